@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — forward+backward throughput of the MI355X-native Gaussian-splat rasterizer.
 
-    python bench.py --gpus N --steps K --warmup W [--config config3] [--adam]
+    python bench.py --gpus N --steps K --warmup W [--config config3] [--adam] [--dump-outputs DIR] [--full]
 
 With N > 1 and no external launcher (RANK unset) the script starts its N ranks itself (self_launch: N fresh child
 processes, one GPU each; the parent never touches a GPU); under `python -m torch.distributed.run ... bench.py --gpus N`
@@ -14,16 +14,25 @@ config4).  Inputs (parameters, dL_dcolor) are resident in HBM before the timed
 region.  Default workload = BASELINE.json configs[2]: 1 M synthetic Gaussians, 1920x1080, SH
 degree 3 (scene generator: cuda-gaussian-splatting_amd/scene.py).
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
+Rank 0 prints ONE JSON line.  Besides the driver's fields (metric, value, unit, higher_is_better, dtype, ms_per_step =
+the wall time of the K timed steps / K) it carries
   roofline      — the dominant kernel: ALGORITHMIC bytes per launch (SURVEY §8d per-unit figures x this
                   run's N, P, pixels) / its mean duration from HIP events recorded on the launch stream
                   inside the timed region (on every 4th timed step: an event between two kernels costs ~5 us
                   of idle device); peak = 8.0 TB/s HBM3E (MI355X_MICROARCH.md);
   frame_roofline— the same for the whole fwd+bwd frame (the north-star target is stated on it);
   stages_ms     — mean per-stage durations from the same events;
+and, with --full only (each takes runs of its own, after the timed region):
   cpu_baseline  — the CPU oracle (a port of the reference's CUDA kernels; the reference has no CPU path)
                   timed on this box's host cores on a bounded sample of the same workload;
   parity        — max-rel-err of RGB and gradients vs the oracle on a reduced scene (checker, not timed).
+A plain run (no --full) sets up, spins up, warms up, times the K steps, writes --dump-outputs and prints the line.
+
+--dump-outputs DIR writes what the last timed step handed its caller, as DIR/<name>.npy (float32, integers as
+float64): the per-pixel arrays whole (color, final_T, n_contrib), `total_pairs`, and of every per-Gaussian array
+(the gradients; with an optimizer step the updated parameters) the rows of a fixed seeded sample of DUMP_ROWS
+Gaussians; at most DUMP_LIMIT bytes in all.  The inputs depend only on the arguments: the scene and dL/dcolor are
+seeded, and with an optimizer step the parameters and moments are put back after the time-bound spin-up.
 """
 from __future__ import annotations
 
@@ -110,6 +119,9 @@ ADAM_LR_SCALE = 0.01  # config 4 / --adam: fraction of the reference's default l
 COLOUR_OVERLAP = False # --colour-overlap: geometry + colour halves, the colour half on a side stream under the sort (A/B)
 SPATIAL_ORDER = False # --spatial-tile-order
 KEY_SORT = True      # --unkeyed-sort: the stage-by-stage route (the sort derives its keys from the projection's arrays)
+DUMP_ROWS = 16384    # --dump-outputs: per-Gaussian arrays are written at this many rows (a fixed seeded sample)
+DUMP_SEED = 20261016
+DUMP_LIMIT = 64 * 10**6  # bytes, all files of one --dump-outputs together
 
 
 def timed_step(pkg, model, cam, settings, g, events, exchange, do_allreduce, opt, all_centres=None):
@@ -196,6 +208,45 @@ def timed_step(pkg, model, cam, settings, g, events, exchange, do_allreduce, opt
     if sampled:
         events.append(ev)
     return srt.total_pairs, fwd, grads
+
+
+def step_outputs(result, model, opt) -> dict:
+    """What one step handed its caller, by name: the image side of the forward (per pixel), the pair count, the
+    gradients that were returned (per Gaussian) and, when the step updated the model in place, its parameters."""
+    pairs, fwd, grads = result
+    out = {"total_pairs": torch.tensor([pairs], dtype=torch.int64),
+           "color": fwd.color, "final_T": fwd.final_T, "n_contrib": fwd.n_contrib}
+    if grads is None:          # forward only: render()'s per-Gaussian outputs
+        for k in ("means_2d", "depths", "cov_2d_inv", "radii", "rgb", "opacities_act"):
+            out[k] = getattr(fwd, k)
+    else:
+        for k in ("dL_dpositions", "dL_drotations", "dL_dscales", "dL_dopacities", "dL_dsh_coeffs", "dL_dmeans_2d"):
+            if getattr(grads, k) is not None:
+                out[k] = getattr(grads, k)
+    if opt is not None:
+        for k in ("positions", "rotations", "scales", "opacities", "sh_coeffs"):
+            out[k] = getattr(model, k)
+    return out
+
+
+def dump_outputs(path: str, outputs: dict, n: int) -> None:
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (integer arrays as float64, exact); arrays with one
+    row per Gaussian only at the rows of a fixed seeded sample of DUMP_ROWS Gaussians (the same in every run)."""
+    rows = None
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False))
+    arrays = {}
+    for name, t in outputs.items():
+        if rows is not None and t.dim() >= 1 and t.shape[0] == n:
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 _PROJ_SNIPPET = r"""
@@ -521,8 +572,14 @@ def main():
     ap.add_argument("--no-colour-overlap", action="store_true", help="(default; kept for the round-3 A/B scripts)")
     ap.add_argument("--colour-grid-cap", type=int, default=0,
                     help="development library only (CUGS_HIP_LIBRARY=.../libcugs_hip_dev.so): workgroups of the colour half")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (per-Gaussian arrays "
+                         "at a fixed seeded sample of rows; at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checker legs after the timed region (N = 1): the CPU baseline and the parity "
+                         "probe against the oracle; a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline leg")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: leave out the parity probe")
     ap.add_argument("--cpu-rows", type=int, default=368,
                     help="image rows blended by the CPU baseline sample (default: a third of a 1080p frame; the "
                          "whole leg, repeated three times, takes ~15 s)")
@@ -537,6 +594,8 @@ def main():
     launched = "RANK" in os.environ and "MASTER_PORT" in os.environ      # under torch.distributed.run / self_launch
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and not launched:
         # no external launcher: start the N ranks ourselves, BEFORE anything in this process touches a GPU
         if not args.launcher_dry_run:
@@ -633,6 +692,13 @@ def main():
     # short timed region must not straddle either.
     # Under a launcher every rank must run the SAME number of steps (each one holds collectives): the ranks agree on
     # the elapsed time (MAX over ranks) after every spin-up step.
+    # With an optimizer step every step moves the model; the spin-up runs for a time, not a number of steps, so the
+    # parameters, moments and step count are put back after it (and after the calibration): the timed steps then see
+    # the same inputs in every run with the same arguments.
+    saved = None
+    if opt is not None:
+        saved = ([getattr(model, k).clone() for k in opt._names], [t.clone() for t in opt.m_],
+                 [t.clone() for t in opt.v_], opt.step_count_)
     spin_t0, spin_steps = time.perf_counter(), 0
     while args.spinup_ms > 0:
         spin_ms = (time.perf_counter() - spin_t0) * 1e3
@@ -667,6 +733,11 @@ def main():
         real = [i for i, m in enumerate(modes) if m != "none"]
         exchange["mode"] = modes[min(real, key=lambda i: cal[i])]                   # ties: the earlier mode
         exchange["calibration_ms"] = {m: round(c_, 4) for m, c_ in zip(modes, cal)}
+    if saved is not None:
+        params, m_, v_, opt.step_count_ = saved
+        for dst, src in zip([getattr(model, k) for k in opt._names] + opt.m_ + opt.v_, params + m_ + v_):
+            dst.copy_(src)
+        del saved, params, m_, v_
 
     for _ in range(args.warmup):
         step(None)
@@ -677,13 +748,21 @@ def main():
     # recorded on every 4th timed step, which is plenty for the stage averages and the roofline figure
     stride = 4 if args.steps >= 8 else 1
     for k in range(args.steps):
-        pairs, _, _ = step(events if k % stride == 0 else None)
+        if k == args.steps - 1:             # the last step's outputs are kept for --dump-outputs
+            last = step(events if k % stride == 0 else None)
+            pairs = last[0]
+        else:
+            pairs, _, _ = step(events if k % stride == 0 else None)
     fence()
     elapsed = time.perf_counter() - t0
     if launched:                                          # MAX over ranks
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(last, model, opt), wl.n)
+    del last
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -803,11 +882,13 @@ def main():
                                "timed_region_exposed_ms": round(ms_per_step - base, 4) if base is not None else None,
                                "per_mode": per_mode,
                                "rccl": parse_rccl_log(logs) if logs else {"unparsed_tail": ["no RCCL log file was written"]}}
-        need_oracle = n_gpus == 1 and not (args.no_cpu_baseline and args.no_parity)
-        orc = ge.load_oracle() if need_oracle else None
-        if not args.no_cpu_baseline and n_gpus == 1:      # rank 0 at N=1 only
+        # the checker legs (--full only): runs of their own after the timed region, rank 0 at N=1 only
+        want_cpu = args.full and not args.no_cpu_baseline and n_gpus == 1
+        want_parity = args.full and not args.no_parity and not forward_only and n_gpus == 1
+        orc = ge.load_oracle() if (want_cpu or want_parity) else None
+        if want_cpu:
             out["cpu_baseline"] = cpu_baseline(pkg, orc, wl, arrays, cam, g_host, args.cpu_rows)
-        if not args.no_parity and not forward_only and n_gpus == 1:
+        if want_parity:
             out["parity"] = parity_probe(pkg, orc, dev)
         if stdout_fd is not None:
             sys.stdout.flush()

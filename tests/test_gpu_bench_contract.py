@@ -1,8 +1,9 @@
 """The driver's contract with bench.py, checked on the GPU box: `python bench.py --gpus 1 --steps K --warmup W` prints
 exactly ONE line on stdout, a JSON object with the keys the contract names, measured on the headline workload
 (BASELINE.json configs[2]) through the product's own render / render_backward sequence, with the roofline object for
-the dominant kernel and the parity probe against the oracle.  (The CPU baseline leg is skipped here: ~15 s of host work
-that `tests/test_host_logic.py` and the default `python bench.py` run cover.)"""
+the dominant kernel and, with --full, the parity probe against the oracle.  (The CPU baseline leg is skipped here:
+~15 s of host work that `tests/test_host_logic.py` and `python bench.py --full` cover.)  A plain run carries neither
+checker leg and, with --dump-outputs, writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -14,10 +15,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*flags):
+def _bench(*flags, full=True):
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
-                          "--spinup-ms", "0", "--no-cpu-baseline", *flags], capture_output=True, text=True, timeout=600,
-                         cwd=ROOT)
+                          "--spinup-ms", "0", *(["--full", "--no-cpu-baseline"] if full else []), *flags],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, res.stdout[-2000:]                     # ONE line on stdout
@@ -50,6 +51,24 @@ def test_keyed_and_unkeyed_routes_agree_on_the_workload():
     """`--unkeyed-sort` (stage-by-stage hand-over) and the default (the projection keys the sort) time the same frame."""
     a, b = _bench("--no-parity"), _bench("--no-parity", "--unkeyed-sort")
     assert a["config"]["pairs"] == b["config"]["pairs"] == 8376524
+
+
+def test_plain_run_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline line without the checker
+    legs, and the last timed step's image, pair count and a fixed sample of its gradients as float .npy files."""
+    import numpy as np
+    out = _bench("--dump-outputs", str(tmp_path), full=False)
+    assert "parity" not in out and "cpu_baseline" not in out
+    assert out["steps"] == 8 and out["ms_per_step"] > 0 and out["config"]["pairs"] == 8376524
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(files) == {"total_pairs", "color", "final_T", "n_contrib", "dL_dpositions", "dL_drotations",
+                          "dL_dscales", "dL_dopacities", "dL_dsh_coeffs", "dL_dmeans_2d"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 10**6
+    assert files["total_pairs"].tolist() == [8376524.0]
+    assert files["color"].shape == (1080, 1920, 3) and files["n_contrib"].shape == (1080, 1920)
+    assert files["dL_dsh_coeffs"].shape == (16384, 3, 16) and np.isfinite(files["dL_dsh_coeffs"]).all()
+    assert float(np.abs(files["dL_dpositions"]).max()) > 0.0
 
 
 def test_launched_bench_line_on_one_rank():

@@ -68,3 +68,43 @@ def test_bench_algorithmic_bytes_match_survey_8d():
     assert b["frame"] == sum(b[k] for k in bench.STAGES)
     assert b["adam"] == 28 * 59 * n
     assert b["raster_backward"] == 714_087_824          # the figure the bench line and DESIGN 4.5 quote
+
+
+def test_bench_dump_outputs_samples_and_types(tmp_path):
+    """bench.py --dump-outputs: per-Gaussian arrays at the same seeded rows in every run, other arrays whole, float32 kept,
+    integers written as float64, the byte limit enforced before anything is written."""
+    import importlib.util
+    import os
+    import pytest
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(
+        os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 3 * bench.DUMP_ROWS
+    grad = torch.arange(n * 3, dtype=torch.float32).reshape(n, 3)
+    outs = {"total_pairs": torch.tensor([12345], dtype=torch.int64), "color": torch.rand(4, 5, 3),
+            "n_contrib": torch.arange(20, dtype=torch.int32).reshape(4, 5), "dL_dpositions": grad}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, n)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == set(outs)
+    assert got["total_pairs"].dtype == np.float64 and got["total_pairs"].tolist() == [12345.0]
+    assert got["n_contrib"].dtype == np.float64 and np.array_equal(got["n_contrib"], outs["n_contrib"].numpy())
+    assert got["color"].dtype == np.float32 and np.array_equal(got["color"], outs["color"].numpy())
+    rows = got["dL_dpositions"][:, 0] / 3
+    assert got["dL_dpositions"].shape == (bench.DUMP_ROWS, 3) and len(np.unique(rows)) == bench.DUMP_ROWS
+    assert np.array_equal(got["dL_dpositions"], grad.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(got["dL_dpositions"], np.load(tmp_path / "b" / "dL_dpositions.npy"))   # same rows every run
+    with pytest.raises(RuntimeError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "c"), {"big": torch.zeros(bench.DUMP_LIMIT // 4 + 1)}, n)
+    assert not (tmp_path / "c").exists()
+
+
+def test_bench_rejects_zero_steps():
+    import os
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    res = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "0", "--launcher-dry-run"],
+                         capture_output=True, text=True, timeout=120)
+    assert res.returncode != 0 and "--steps" in res.stderr

@@ -10,7 +10,7 @@ O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py --no-cpu-baseline --no-parity"
-python3 $R/bench.py --steps 200 --warmup 20 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python3 $R/bench.py --full --steps 200 --warmup 20 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 $B --config config2 --steps 20 --warmup 5 > $O/${TAG}_bench_config2.json 2>> $O/${TAG}_bench.err
 $B --config config4 --steps 40 --warmup 5 > $O/${TAG}_bench_config4.json 2>> $O/${TAG}_bench.err
 $B --mu-s -3.5 --steps 100 --warmup 10 > $O/${TAG}_bench_dense.json 2>> $O/${TAG}_bench.err
