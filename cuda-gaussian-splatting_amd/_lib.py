@@ -44,10 +44,22 @@ class DensifyArray(C.Structure):
 
 DENSIFY_COPY, DENSIFY_POSITIONS, DENSIFY_SCALES, DENSIFY_STATE = 0, 1, 2, 3
 
+
+class McmcFused(C.Structure):
+    """struct cugs_mcmc_fused."""
+    _fields_ = [("lambda_opacity", C.c_float), ("lambda_scale", C.c_float), ("noise_lr", C.c_float),
+                ("gate_k", C.c_float), ("gate_t", C.c_float), ("step", C.c_uint32), ("seed", C.c_uint64),
+                ("noise", C.c_void_p)]
+
+
+MCMC_STREAM_NOISE, MCMC_STREAM_JITTER, MCMC_STREAM_SAMPLE = 0, 1, 2     # CUGS_MCMC_STREAM_*
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
 _F = C.c_float
+_U32 = C.c_uint32
+_U64 = C.c_uint64
 
 # name -> (restype, argtypes); must list every function of include/cugs_hip.h
 SIGNATURES = {
@@ -105,6 +117,14 @@ SIGNATURES = {
     "cugs_densify_workspace_bytes": (C.c_size_t, [_L]),
     "cugs_densify_plan": (_I, [_L, _P, _P, C.c_size_t, C.POINTER(C.c_int64), _P]),
     "cugs_densify_apply": (_I, [_L, _L, _P, C.c_size_t, _P, _P, C.POINTER(DensifyArray), _I, _P]),
+    "cugs_mcmc_random_bits": (_I, [_U64, _U32, _U32, _U64, _L, _P, _P]),
+    "cugs_mcmc_regularization": (_I, [_L, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cugs_mcmc_inject_noise": (_I, [_L, _P, _P, _P, _F, _F, _F, _P, _U64, _U32, _P]),
+    "cugs_mcmc_relocate_workspace_bytes": (C.c_size_t, [_L]),
+    "cugs_mcmc_relocate": (_I, [_L, _I, _P, _P, _P, _P, _P, _F, _F, _F, _U64, _U32, C.POINTER(_P), C.POINTER(_P), _P,
+                                C.c_size_t, _P, _P, _P]),
+    "cugs_project_backward_adam_mcmc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
+                                             C.POINTER(AdamFused), C.POINTER(McmcFused), _P, _P]),
     "cugs_ply_vertex_floats": (_I, [_I, _I]),
     "cugs_ply_pack": (_I, [_L, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     "cugs_ply_unpack": (_I, [_L, _I, _I, _P, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),

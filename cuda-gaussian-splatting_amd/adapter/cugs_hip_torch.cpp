@@ -461,7 +461,10 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
 }
 
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& ro, const ModelTensors& model,
-                               const cugs_camera& camera, const RenderSettings& settings, FusedAdam* fused) {
+                               const cugs_camera& camera, const RenderSettings& settings, FusedAdam* fused,
+                               const MCMCController* mcmc, int step) {
+    TORCH_CHECK(!mcmc || fused, "the fused MCMC route needs the FusedAdam (otherwise: compute_regularization, step, "
+                "inject_noise)");
     TORCH_CHECK(dL_dcolor.is_cuda(), "dL_dcolor must be on CUDA device");                             // rasterizer.cpp:122-124
     TORCH_CHECK(dL_dcolor.dim() == 3 && dL_dcolor.size(2) == 3, "dL_dcolor must be [H, W, 3]");
     const int64_t n = model.positions.size(0);
@@ -500,6 +503,17 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                     "the fused optimizer step needs the colour_gate of cugs_hip::render");
         const cugs_adam_fused adam = fused->begin_fused_step();
         auto radii = ro.radii.contiguous(), gate = ro.colour_gate.contiguous();
+        if (mcmc) {
+            const cugs_mcmc_fused mc = mcmc->fused_args(step);
+            check(cugs_project_backward_adam_mcmc(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
+                                                  ptr<float>(model.positions), ptr<float>(model.rotations),
+                                                  ptr<float>(model.scales), ptr<float>(model.opacities),
+                                                  ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate),
+                                                  &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam, &mc,
+                                                  ptr<float>(o.dL_dmeans_2d), stream_of(dL_dcolor)),
+                  "cugs_project_backward_adam_mcmc");
+            return o;
+        }
         check(cugs_project_backward_adam(n, static_cast<int>(model.sh_coeffs.size(2)), degree, ptr<float>(model.positions),
                                          ptr<float>(model.rotations), ptr<float>(model.scales), ptr<float>(model.opacities),
                                          ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate), &camera,
@@ -869,6 +883,108 @@ ModelTensors read_gaussian_ply(const std::string& path, const torch::Device& dev
         optimizer->step_count_ = static_cast<int>(step);
     }
     return m;
+}
+
+// ---- N5: MCMC densification (optimizer/mcmc_densification.cpp) ----
+namespace {
+void check_model(const ModelTensors& m, const char* what) {
+    for (const torch::Tensor* t : {&m.positions, &m.sh_coeffs, &m.opacities, &m.rotations, &m.scales})
+        TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous(), what,
+                    ": the model tensors must be contiguous float32 CUDA tensors (updated in place)");
+}
+}  // namespace
+
+bool MCMCController::should_relocate(int step) const {                                      // :30-34
+    return step >= config_.relocate_from && step <= config_.relocate_until && step % config_.relocate_every == 0;
+}
+
+float MCMCController::noise_lr(int step) const {                                             // :40-50
+    if (step >= config_.noise_lr_max_steps) return config_.noise_lr_final;
+    if (step <= 0) return config_.noise_lr_init;
+    const float t = static_cast<float>(step) / static_cast<float>(config_.noise_lr_max_steps);
+    const float log_ratio = std::log(config_.noise_lr_final / config_.noise_lr_init);
+    return config_.noise_lr_init * std::exp(t * log_ratio);
+}
+
+MCMCStats MCMCController::relocate(ModelTensors& model, int step, FusedAdam* optimizer, const torch::Tensor& sources_out) {
+    MCMCStats stats;
+    const int64_t n = model.positions.defined() ? model.positions.size(0) : 0;
+    stats.num_total = static_cast<int>(n);
+    if (n == 0) return stats;
+    check_model(model, "relocate");
+    const auto dev = model.positions.device();
+    float* m[5];
+    float* v[5];
+    if (optimizer) {
+        TORCH_CHECK(optimizer->params_[0].data_ptr() == model.positions.data_ptr(),
+                    "relocate: the optimizer must have been built on this model");
+        for (int g = 0; g < 5; ++g) {
+            TORCH_CHECK(optimizer->m_[g].is_contiguous() && optimizer->v_[g].is_contiguous(),
+                        "relocate: the optimizer moments must be contiguous");
+            m[g] = optimizer->m_[g].data_ptr<float>();
+            v[g] = optimizer->v_[g].data_ptr<float>();
+        }
+    }
+    if (sources_out.defined())
+        TORCH_CHECK(sources_out.is_cuda() && sources_out.scalar_type() == torch::kInt32 && sources_out.numel() >= n &&
+                    sources_out.is_contiguous(), "sources_out must be a contiguous int32 CUDA tensor of N");
+    auto ws = workspace(dev, cugs_mcmc_relocate_workspace_bytes(n), 5);
+    auto out = torch::zeros({2}, iopt(model.positions));
+    check(cugs_mcmc_relocate(n, static_cast<int>(model.sh_coeffs.size(2)), ptr<float>(model.positions),
+                             ptr<float>(model.rotations), ptr<float>(model.scales), ptr<float>(model.opacities),
+                             ptr<float>(model.sh_coeffs), config_.dead_opacity_threshold, config_.relocate_cap,
+                             scene_extent_, config_.seed, static_cast<uint32_t>(step), optimizer ? m : nullptr,
+                             optimizer ? v : nullptr, ws.data_ptr(), static_cast<size_t>(ws.numel()), ptr<int32_t>(out),
+                             sources_out.defined() ? sources_out.data_ptr<int32_t>() : nullptr,
+                             stream_of(model.positions)),
+          "cugs_mcmc_relocate");
+    auto host = out.to(torch::kCPU);
+    stats.num_dead = host[0].item<int>();
+    stats.num_relocated = host[1].item<int>();
+    return stats;
+}
+
+void MCMCController::inject_noise(ModelTensors& model, int step, const torch::Tensor& noise_in) const {   // :144-161
+    const int64_t n = model.positions.defined() ? model.positions.size(0) : 0;
+    if (n == 0) return;
+    check_model(model, "inject_noise");
+    torch::Tensor noise;
+    if (noise_in.defined()) {
+        TORCH_CHECK(noise_in.is_cuda() && noise_in.dim() == 2 && noise_in.size(0) == n && noise_in.size(1) == 3,
+                    "noise must be [N, 3] on CUDA");
+        noise = f32c(noise_in);
+    }
+    check(cugs_mcmc_inject_noise(n, ptr<float>(model.positions), ptr<float>(model.scales), ptr<float>(model.opacities),
+                                 noise_lr(step), config_.noise_gate_k, config_.noise_gate_t,
+                                 noise.defined() ? ptr<float>(noise) : nullptr, config_.seed, static_cast<uint32_t>(step),
+                                 stream_of(model.positions)),
+          "cugs_mcmc_inject_noise");
+}
+
+torch::Tensor MCMCController::compute_regularization(const ModelTensors& model, torch::Tensor& reg_dL_dopacities,
+                                                     torch::Tensor& reg_dL_dscales) const {     // :167-186
+    const int64_t n = model.positions.size(0);
+    auto value = torch::zeros({}, fopt(model.positions));
+    reg_dL_dopacities = torch::empty({n, 1}, fopt(model.positions));
+    reg_dL_dscales = torch::empty({n, 3}, fopt(model.positions));
+    if (n == 0) return value;
+    auto opa = f32c(model.opacities), scl = f32c(model.scales);
+    auto ws = workspace(model.positions.device(), cugs_mcmc_relocate_workspace_bytes(0), 6);
+    check(cugs_mcmc_regularization(n, ptr<float>(opa), ptr<float>(scl), config_.lambda_opacity, config_.lambda_scale,
+                                   nullptr, nullptr, ptr<float>(reg_dL_dopacities), ptr<float>(reg_dL_dscales),
+                                   ptr<float>(value), ws.data_ptr(), static_cast<size_t>(ws.numel()),
+                                   stream_of(model.positions)),
+          "cugs_mcmc_regularization");
+    return value;
+}
+
+cugs_mcmc_fused MCMCController::fused_args(int step, const torch::Tensor& noise) const {
+    cugs_mcmc_fused a{};
+    a.lambda_opacity = config_.lambda_opacity; a.lambda_scale = config_.lambda_scale;
+    a.noise_lr = noise_lr(step); a.gate_k = config_.noise_gate_k; a.gate_t = config_.noise_gate_t;
+    a.step = static_cast<uint32_t>(step); a.seed = config_.seed;
+    a.noise = noise.defined() ? noise.data_ptr<float>() : nullptr;
+    return a;
 }
 
 }  // namespace cugs_hip

@@ -93,12 +93,16 @@ torch::Tensor evaluate_sh_backward_cuda(int degree, const torch::Tensor& sh_coef
 RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
                     bool for_backward = true);
 class FusedAdam;
+class MCMCController;
 // `fused` (optional, not in the reference; single-GPU training): the projection backward applies the optimizer step to
 // the model in place (cugs_project_backward_adam) and the five parameter gradients are never materialised (undefined
 // in the result; dL_dmeans_2d is returned) - bit for bit render_backward + apply_gradients + step.
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& render_out,
                                const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
-                               FusedAdam* fused = nullptr);
+                               FusedAdam* fused = nullptr, const MCMCController* mcmc = nullptr, int step = 0);
+// `mcmc` (with `fused` only): the regulariser gradient and the position noise of iteration `step` ride in
+// the same launch (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + compute_regularization's
+// gradients, apply_gradients, step, inject_noise(model, step).
 
 // training/loss.hpp:21-52 + the autograd step of trainer.cpp:214-217 in two launches.
 // Scalars are 0-dim device tensors, as in the reference.
@@ -124,6 +128,7 @@ public:
     const std::array<torch::Tensor, 5>& params() const { return params_; }
 private:
     friend class DensificationController;      // carries m_/v_ through clone/split/prune
+    friend class MCMCController;               // zeroes the relocated rows' moments
     friend bool write_gaussian_ply(const std::string&, const ModelTensors&, const FusedAdam*);
     friend ModelTensors read_gaussian_ply(const std::string&, const torch::Device&, FusedAdam*);
     std::array<torch::Tensor, 5> params_, m_, v_, grads_;
@@ -158,6 +163,41 @@ private:
     DensificationConfig config_;
     float scene_extent_;
     torch::Tensor grad_accum_, grad_count_, max_radii_2d_;
+};
+
+// optimizer/mcmc_densification.hpp:27-170 over csrc/mcmc.hip.  Same schedule and statistics as the
+// reference; the random draws come from the counter-based generator keyed by (seed, step) (cugs_hip.h N5 block), the
+// sampling weights are quantised to 2^-24, and the VRAM guard is not mirrored.  N never changes.
+struct MCMCConfig {
+    int relocate_from = 500, relocate_until = 15000, relocate_every = 100;
+    float dead_opacity_threshold = 0.005f, relocate_cap = 0.05f;
+    float noise_lr_init = 5e5f, noise_lr_final = 1e3f;
+    int noise_lr_max_steps = 30000;
+    float noise_gate_k = 100.0f, noise_gate_t = 0.995f;
+    float lambda_opacity = 0.01f, lambda_scale = 0.01f;
+    uint64_t seed = 0;                                     // not in the reference: the generator's key
+};
+struct MCMCStats { int num_relocated = 0, num_dead = 0, num_total = 0; bool skipped_vram = false; };
+class MCMCController {
+public:
+    MCMCController(const MCMCConfig& config, float scene_extent) : config_(config), scene_extent_(scene_extent) {}
+    bool should_relocate(int step) const;
+    float noise_lr(int step) const;
+    // in place, N constant; one 8-byte read-back.  `optimizer` (optional): the relocated rows' moments are zeroed.
+    // `sources_out` (optional, int32 [N] device): the source row of the j-th relocated row.
+    MCMCStats relocate(ModelTensors& model, int step, FusedAdam* optimizer = nullptr,
+                       const torch::Tensor& sources_out = {});
+    // `noise` (optional, [N, 3] standard normals): replaces the generator's draw
+    void inject_noise(ModelTensors& model, int step, const torch::Tensor& noise = {}) const;
+    // the value as a 0-dim device tensor (no host sync; the reference returns reg_loss.item())
+    torch::Tensor compute_regularization(const ModelTensors& model, torch::Tensor& reg_dL_dopacities,
+                                         torch::Tensor& reg_dL_dscales) const;
+    // the fused route's arguments (render_backward(..., &adam, &mcmc, step))
+    cugs_mcmc_fused fused_args(int step, const torch::Tensor& noise = {}) const;
+    const MCMCConfig& config() const { return config_; }
+private:
+    MCMCConfig config_;
+    float scene_extent_;
 };
 
 // the float [height, width, 3] training target from a device-resident uint8 [h, w, 3] view - x 1/255

@@ -676,7 +676,8 @@ def render(model: GaussianModel, camera: CameraInfo, settings: RenderSettings, f
 def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: GaussianModel,
                     camera: CameraInfo, settings: RenderSettings,
                     dL_drgb_gated_out: Optional[torch.Tensor] = None,
-                    geom_flat: Optional[torch.Tensor] = None, fused_adam=None, on_gated_ready=None) -> BackwardOutput:
+                    geom_flat: Optional[torch.Tensor] = None, fused_adam=None, on_gated_ready=None,
+                    mcmc=None, mcmc_step: int = 0, mcmc_noise: Optional[torch.Tensor] = None) -> BackwardOutput:
     """`dL_drgb_gated_out` ([N,3], optional, not in the reference): when given, the per-view SH gradient
     is NOT materialised (dL_dsh_coeffs is None) and the gated colour gradient is written there instead,
     for parallel.exchange_gradients() to rebuild the summed SH gradient after the all-gather.
@@ -686,7 +687,10 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
     `fused_adam` (a FusedAdam built on `model`, optional, not in the reference): single-GPU training - the
     projection backward applies the optimizer step to the model IN PLACE (cugs_project_backward_adam) and the
     five parameter gradients are never materialised (they are None in the result; dL_dmeans_2d is returned).
-    Equivalent, bit for bit, to render_backward + apply_gradients + step."""
+    Equivalent, bit for bit, to render_backward + apply_gradients + step.
+    `mcmc` (an MCMCController, with fused_adam only): the per-iteration MCMC work rides in the same launch
+    (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + the gradients of
+    mcmc.compute_regularization, apply_gradients, step, mcmc.inject_noise(model, mcmc_step, mcmc_noise)."""
     _torch_check(dL_dcolor.is_cuda, "dL_dcolor must be on CUDA device")
     _torch_check(dL_dcolor.dim() == 3 and dL_dcolor.shape[2] == 3, "dL_dcolor must be [H, W, 3]")
     n = model.num_gaussians()
@@ -717,15 +721,25 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
         _torch_check(dL_drgb_gated_out is None and geom_flat is None,
                      "the fused optimizer step is for single-GPU training (no gradient exchange)")
         _torch_check(render_out.colour_gate is not None, "the fused optimizer step needs render()'s colour_gate")
+        if mcmc_noise is not None:
+            _torch_check(mcmc is not None, "mcmc_noise needs mcmc")
+            _torch_check(tuple(mcmc_noise.shape) == (n, 3) and mcmc_noise.is_cuda, "mcmc_noise must be [N, 3] on CUDA")
+            mcmc_noise = mcmc_noise.contiguous().to(torch.float32)
         adam = fused_adam.begin_fused_step()
         cam = camera.to_abi()
-        check(lib.cugs_project_backward_adam(n, int(model.sh_coeffs.shape[2]), active_degree, _ptr(model.positions),
-                                             _ptr(model.rotations), _ptr(model.scales), _ptr(model.opacities),
-                                             _ptr(model.sh_coeffs), _ptr(render_out.radii.contiguous()),
-                                             _ptr(render_out.colour_gate.contiguous()), C.byref(cam),
-                                             float(settings.scale_modifier), _ptr(rb.grad_accum), C.byref(adam),
-                                             _ptr(d_means_2d), _stream(dev)), "cugs_project_backward_adam")
+        args = (n, int(model.sh_coeffs.shape[2]), active_degree, _ptr(model.positions), _ptr(model.rotations),
+                _ptr(model.scales), _ptr(model.opacities), _ptr(model.sh_coeffs), _ptr(render_out.radii.contiguous()),
+                _ptr(render_out.colour_gate.contiguous()), C.byref(cam), float(settings.scale_modifier),
+                _ptr(rb.grad_accum), C.byref(adam))
+        if mcmc is not None:
+            mc = mcmc.fused_args(mcmc_step, mcmc_noise)
+            check(lib.cugs_project_backward_adam_mcmc(*args, C.byref(mc), _ptr(d_means_2d), _stream(dev)),
+                  "cugs_project_backward_adam_mcmc")
+        else:
+            check(lib.cugs_project_backward_adam(*args, _ptr(d_means_2d), _stream(dev)), "cugs_project_backward_adam")
         return BackwardOutput(None, None, None, None, None, d_means_2d)
+    _torch_check(mcmc is None, "the fused MCMC route needs fused_adam (otherwise: compute_regularization, "
+                 "step, inject_noise)")
     gated_by_projection = dL_drgb_gated_out
     if on_gated_ready is not None:
         _torch_check(dL_drgb_gated_out is not None, "on_gated_ready needs dL_drgb_gated_out")

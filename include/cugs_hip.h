@@ -450,6 +450,69 @@ int cugs_ply_unpack(int64_t n, int num_coeffs, int num_props, const float* verti
 int cugs_image_to_float(int src_width, int src_height, const uint8_t* src_rgb8, int dst_width, int dst_height,
                         float* dst, void* stream);
 
+/* ---- N5: MCMC densification (optimizer/mcmc_densification.cpp) ---------------------------------
+ * Random draws come from a counter-based Philox4x32-10: key (seed_lo, seed_hi), counter (index_lo, index_hi,
+ * stream_id, step).  One call per index gives four words; u = ((x >> 8) + 1) * 2^-24 in (0, 1]; Box-Muller on
+ * (u0, u1) and (u2, u3), the first three normals used.  Streams: NOISE (index = Gaussian), JITTER (index =
+ * relocated row), SAMPLE (index = ordinal of the relocation; r64 = w1 << 32 | w0).  They replace randn_like /
+ * multinomial (:60-138, :158), whose draws cannot be reproduced; the same (seed, step) gives the same bits on
+ * every replica and every route.
+ * cugs_mcmc_random_bits: out[4 j + w] = word w of the draw for index first_index + j (pins the generator).
+ * cugs_mcmc_regularization: compute_regularization (:167-186) without autograd or a host sync:
+ *   out_o[i] = base_o[i] + ((lambda_o / N) * (1 - y)) * y, y = sigmoid(opacities[i])      [N, 1]
+ *   out_s[i] = base_s[i] + (lambda_s / (3N)) * exp(scales[i])                             [N, 3]
+ *   base NULL = write the regulariser gradient alone; base == out adds in place; outs NULL = value only.
+ *   value_out (device float, may be NULL) = lambda_o mean(y) + lambda_s mean(exp s), a fixed-order two-level
+ *   reduction (double partials) through a small workspace (below).
+ * cugs_mcmc_inject_noise: inject_noise (:144-161): positions += ((lr * exp(s)) * gate) * n,
+ *   gate = sigmoid(-gate_k * (sigmoid(opa) - gate_t)); n = noise [N, 3] when given, else stream NOISE.
+ * cugs_mcmc_relocate: relocate (:56-138) in place, N constant.  Dead = sigmoid(opa) < dead_threshold;
+ *   M = min(num_dead, (int)(relocate_cap * (float)N)); the first M dead rows in index order are relocated
+ *   (none when num_dead or num_alive is 0).  Sources are drawn with replacement over the alive rows weighted by
+ *   w_i = rintf(y_i * 2^24) (uint64 inclusive scan cdf; x = mulhi64(r64, total); the first i with cdf[i] > x).
+ *   Per relocated row: rotation and SH copied; pos = src_pos + (n * scene_extent) * 0.01f (stream JITTER);
+ *   scale = src_scale - logf(10); opacity = logf(0.01f / 0.99f).  m / v (host arrays of five device pointers in
+ *   ParamGroup order, both NULL = untouched, as the reference, trainer.cpp:265): the relocated rows' Adam moments
+ *   are zeroed.  stats (device int32[2]) = {num_dead, num_relocated}; src_out (device int32 [N], may be NULL):
+ *   source row of the j-th relocated row, j < num_relocated.  No host sync.  Workspace:
+ *   cugs_mcmc_relocate_workspace_bytes(n).  cugs_mcmc_regularization needs cugs_mcmc_relocate_workspace_bytes(0)
+ *   bytes (16 KB of partial sums) whatever n; a relocation workspace serves it too.
+ * cugs_project_backward_adam_mcmc: cugs_project_backward_adam with the per-iteration MCMC work fused in, bit for
+ *   bit the sequence regulariser (add) -> Adam step -> inject_noise: the regulariser gradient joins the opacity
+ *   and scale gradients of every Gaussian, and the noise (from the updated opacity and scales) the updated position.
+ */
+#define CUGS_MCMC_STREAM_NOISE 0u
+#define CUGS_MCMC_STREAM_JITTER 1u
+#define CUGS_MCMC_STREAM_SAMPLE 2u
+typedef struct cugs_mcmc_fused {
+    float lambda_opacity;
+    float lambda_scale;
+    float noise_lr;
+    float gate_k;
+    float gate_t;
+    uint32_t step;
+    uint64_t seed;
+    const float* noise;    /* [n, 3] explicit standard normals (device), or NULL: the generator */
+} cugs_mcmc_fused;
+int cugs_mcmc_random_bits(uint64_t seed, uint32_t stream_id, uint32_t step, uint64_t first_index, int64_t count,
+                          uint32_t* out, void* stream);
+int cugs_mcmc_regularization(int64_t n, const float* opacities, const float* scales, float lambda_opacity,
+                             float lambda_scale, const float* base_dL_dopacities, const float* base_dL_dscales,
+                             float* dL_dopacities, float* dL_dscales, float* value_out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int cugs_mcmc_inject_noise(int64_t n, float* positions, const float* scales, const float* opacities, float noise_lr,
+                           float gate_k, float gate_t, const float* noise, uint64_t seed, uint32_t step, void* stream);
+size_t cugs_mcmc_relocate_workspace_bytes(int64_t n);
+int cugs_mcmc_relocate(int64_t n, int num_coeffs, float* positions, float* rotations, float* scales, float* opacities,
+                       float* sh_coeffs, float dead_threshold, float relocate_cap, float scene_extent, uint64_t seed,
+                       uint32_t step, float* const m[5], float* const v[5], void* workspace, size_t workspace_bytes,
+                       int32_t* stats, int32_t* src_out, void* stream);
+int cugs_project_backward_adam_mcmc(int64_t n, int num_coeffs, int active_degree, float* positions, float* rotations,
+                                    float* scales, float* opacities, float* sh_coeffs, const int32_t* radii,
+                                    const uint8_t* colour_gate, const cugs_camera* camera_host, float scale_modifier,
+                                    const float* grad_accum, const cugs_adam_fused* adam_host,
+                                    const cugs_mcmc_fused* mcmc_host, float* dL_dmeans_2d_out, void* stream);
+
 /* Device properties the host side needs without linking the HIP runtime itself. */
 int cugs_device_count(int* count_host);
 
