@@ -93,6 +93,10 @@ SIGNATURES = {
                                             _P, _P, _P, _P, C.c_size_t, _P, _P]),
     "cugs_rasterize_backward_ordered": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                              _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "cugs_rasterize_forward_depth": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
+    "cugs_rasterize_backward_depth": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cugs_rasterize_forward": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P]),
     "cugs_rasterize_forward_zero": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,

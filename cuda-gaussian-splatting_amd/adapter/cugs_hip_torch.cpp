@@ -162,12 +162,17 @@ ForwardOutput rasterize_forward(const torch::Tensor& means_2d, const torch::Tens
                                 const torch::Tensor& opacities, const torch::Tensor& tile_ranges,
                                 const torch::Tensor& gaussian_indices, int img_w, int img_h,
                                 const float background[3], const torch::Tensor& packed, const torch::Tensor& zero_buf,
-                                const torch::Tensor& tile_order) {
+                                const torch::Tensor& tile_order, const torch::Tensor& depths) {
     TORCH_CHECK(means_2d.is_cuda(), "means_2d must be on CUDA");
     ForwardOutput o;
     o.color = torch::empty({img_h, img_w, 3}, fopt(means_2d));
     o.final_T = torch::empty({img_h, img_w}, fopt(means_2d));
     o.n_contrib = torch::empty({img_h, img_w}, iopt(means_2d));
+    if (depths.defined()) {
+        TORCH_CHECK(depths.is_cuda() && depths.device() == means_2d.device() && depths.dim() == 1 &&
+                    depths.size(0) == means_2d.size(0), "depths must be [N] on the device of means_2d");
+        o.depth_map = torch::empty({img_h, img_w}, fopt(means_2d));        // every pixel is written
+    }
     if (img_w == 0 || img_h == 0) {
         if (zero_buf.defined()) zero_buf.zero_();             // the promise holds without a blend launch too
         return o;
@@ -177,9 +182,23 @@ ForwardOutput rasterize_forward(const torch::Tensor& means_2d, const torch::Tens
     if (zero_buf.defined())                                     // the blend also clears the backward's accumulator
         TORCH_CHECK(zero_buf.is_contiguous() && zero_buf.scalar_type() == torch::kFloat32 && zero_buf.numel() % 4 == 0,
                     "zero_buf must be a contiguous float32 tensor of a multiple of four elements");
-    if (tile_order.defined()) {                                 // workgroups handed out longest tile list first
+    if (tile_order.defined())
         TORCH_CHECK(tile_order.is_contiguous() && tile_order.scalar_type() == torch::kInt32 &&
                     tile_order.numel() == 4 * tr.size(0), "tile_order must be a contiguous [tiles, 4] int32 tensor");
+    if (depths.defined()) {                                     // the depth map too
+        auto z = depths.contiguous().to(torch::kFloat32);
+        check(cugs_rasterize_forward_depth(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
+                                           ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(o.color),
+                                           ptr<float>(o.final_T), ptr<int32_t>(o.n_contrib),
+                                           zero_buf.defined() ? zero_buf.data_ptr() : nullptr,
+                                           zero_buf.defined() ? static_cast<size_t>(zero_buf.numel()) * sizeof(float) : 0,
+                                           tile_order.defined() ? reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>())
+                                                                : nullptr,
+                                           ptr<float>(z), ptr<float>(o.depth_map), stream_of(means_2d)),
+              "cugs_rasterize_forward_depth");
+        return o;
+    }
+    if (tile_order.defined()) {                                 // workgroups handed out longest tile list first
         check(cugs_rasterize_forward_ordered(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
                                              ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(o.color),
                                              ptr<float>(o.final_T), ptr<int32_t>(o.n_contrib),
@@ -220,10 +239,22 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
                                            const torch::Tensor& gaussian_indices, const torch::Tensor& final_T,
                                            const torch::Tensor& n_contrib, int img_w, int img_h,
                                            const float background[3], int n_gaussians, const torch::Tensor& packed,
-                                           bool unpack, const torch::Tensor& zeroed_accum, const torch::Tensor& tile_order) {
+                                           bool unpack, const torch::Tensor& zeroed_accum, const torch::Tensor& tile_order,
+                                           const torch::Tensor& depths, const torch::Tensor& dL_ddepth_map,
+                                           const torch::Tensor& dL_dalpha) {
     TORCH_CHECK(dL_dcolor.is_cuda(), "dL_dcolor must be on CUDA");
     const int64_t n = n_gaussians;
     RasterizeBackwardOutput o;
+    const bool depth_route = depths.defined() || dL_ddepth_map.defined() || dL_dalpha.defined();
+    if (depth_route) {
+        TORCH_CHECK(depths.defined(), "the depth / alpha map gradients need the projection's depths");
+        TORCH_CHECK(depths.is_cuda() && depths.device() == dL_dcolor.device() && depths.dim() == 1 && depths.size(0) == n,
+                    "depths must be [N] on the device of dL_dcolor");
+        for (const torch::Tensor* t : {&dL_ddepth_map, &dL_dalpha})
+            if (t->defined())
+                TORCH_CHECK(t->is_cuda() && t->device() == dL_dcolor.device() && t->dim() == 2 && t->size(0) == img_h &&
+                            t->size(1) == img_w, "dL_ddepth_map / dL_dalpha must be [H, W] on the device of dL_dcolor");
+    }
     const bool prezeroed = zeroed_accum.defined();
     if (prezeroed)
         TORCH_CHECK(zeroed_accum.is_contiguous() && zeroed_accum.dim() == 2 && zeroed_accum.size(0) == n &&
@@ -234,14 +265,32 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
         o.dL_dopacity_act = torch::empty({n}, fopt(dL_dcolor));
         o.dL_dmeans_2d = torch::empty({n, 2}, fopt(dL_dcolor));
         o.dL_dcov_2d_inv = torch::empty({n, 3}, fopt(dL_dcolor));
+        if (depth_route) o.dL_ddepths = torch::empty({n}, fopt(dL_dcolor));
     }
     if (n == 0) return o;
     auto g = dL_dcolor.contiguous(), m = means_2d.contiguous(), c = cov_2d_inv.contiguous(), r = rgb.contiguous();
     auto op = opacities.contiguous(), tr = tile_ranges.contiguous(), gi = gaussian_indices.contiguous();
     auto ft = final_T.contiguous(), nc = n_contrib.contiguous();
-    if (tile_order.defined()) {
+    if (tile_order.defined())
         TORCH_CHECK(tile_order.is_contiguous() && tile_order.scalar_type() == torch::kInt32 &&
                     tile_order.numel() == 4 * tr.size(0), "tile_order must be a contiguous [tiles, 4] int32 tensor");
+    if (depth_route) {
+        auto z = depths.contiguous().to(torch::kFloat32);
+        auto f32 = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
+        auto dd = f32(dL_ddepth_map), da = f32(dL_dalpha);
+        check(cugs_rasterize_backward_depth(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
+                                            ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g),
+                                            ptr<float>(ft), ptr<int32_t>(nc), n, ptr<float>(o.grad_accum),
+                                            ptr<float>(o.dL_drgb), ptr<float>(o.dL_dopacity_act), ptr<float>(o.dL_dmeans_2d),
+                                            ptr<float>(o.dL_dcov_2d_inv), prezeroed ? 1 : 0,
+                                            tile_order.defined() ? reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>())
+                                                                 : nullptr,
+                                            ptr<float>(z), ptr<float>(dd), ptr<float>(da), ptr<float>(o.dL_ddepths),
+                                            stream_of(dL_dcolor)),
+              "cugs_rasterize_backward_depth");
+        return o;
+    }
+    if (tile_order.defined()) {
         check(cugs_rasterize_backward_ordered(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
                                               ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g),
                                               ptr<float>(ft), ptr<int32_t>(nc), n, ptr<float>(o.grad_accum),
@@ -344,7 +393,7 @@ static int max_sh_degree(const torch::Tensor& sh) {                             
 }
 
 RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
-                    bool for_backward) {
+                    bool for_backward, bool want_depth_map) {
     TORCH_CHECK(model.positions.defined() && model.positions.is_cuda(), "GaussianModel must be on CUDA device");
     const int64_t n = model.positions.size(0);
     const int w = camera.width, h = camera.height;
@@ -358,6 +407,7 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
         o.cov_2d_inv = torch::empty({0, 3}, fopt(model.positions)); o.radii = torch::empty({0}, iopt(model.positions));
         o.rgb = torch::empty({0, 3}, fopt(model.positions)); o.opacities_act = torch::empty({0}, fopt(model.positions));
         o.gaussian_indices = torch::empty({0}, iopt(model.positions)); o.tile_ranges = torch::empty({0, 2}, iopt(model.positions));
+        if (want_depth_map) o.depth_map = torch::zeros({h, w}, fopt(model.positions));
         return o;
     }
     const int degree = std::min(settings.active_sh_degree, max_sh_degree(model.sh_coeffs));
@@ -378,7 +428,8 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
     torch::Tensor accum = for_backward ? torch::empty({n, CUGS_GRAD_STRIDE}, fopt(model.positions)) : torch::Tensor();
     auto blend = [&](const SortingOutput& s) {
         return rasterize_forward(proj.means_2d, proj.cov_2d_inv, proj.rgb, proj.opacities_act, s.tile_ranges,
-                                 s.gaussian_values_sorted, w, h, settings.background, proj.packed, accum, s.tile_order);
+                                 s.gaussian_values_sorted, w, h, settings.background, proj.packed, accum, s.tile_order,
+                                 want_depth_map ? proj.depths : torch::Tensor());
     };
     SortingOutput srt;
     ForwardOutput fwd;
@@ -449,7 +500,7 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
     }
     // running maximum with a slow decay: views differ by tens of percent, spare capacity is cheap, a miss is not
     state.last_pairs = std::max<int64_t>(srt.total_pairs, prev - prev / 32);
-    o.color = fwd.color; o.final_T = fwd.final_T; o.n_contrib = fwd.n_contrib;
+    o.color = fwd.color; o.final_T = fwd.final_T; o.n_contrib = fwd.n_contrib; o.depth_map = fwd.depth_map;
     o.means_2d = proj.means_2d; o.depths = proj.depths; o.cov_2d_inv = proj.cov_2d_inv; o.radii = proj.radii;
     o.rgb = proj.rgb; o.opacities_act = proj.opacities_act;
     o.gaussian_indices = srt.gaussian_values_sorted; o.tile_ranges = srt.tile_ranges; o.packed = proj.packed;
@@ -462,11 +513,15 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
 
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& ro, const ModelTensors& model,
                                const cugs_camera& camera, const RenderSettings& settings, FusedAdam* fused,
-                               const MCMCController* mcmc, int step) {
+                               const MCMCController* mcmc, int step, const torch::Tensor& dL_ddepth_map,
+                               const torch::Tensor& dL_dalpha) {
     TORCH_CHECK(!mcmc || fused, "the fused MCMC route needs the FusedAdam (otherwise: compute_regularization, step, "
                 "inject_noise)");
     TORCH_CHECK(dL_dcolor.is_cuda(), "dL_dcolor must be on CUDA device");                             // rasterizer.cpp:122-124
     TORCH_CHECK(dL_dcolor.dim() == 3 && dL_dcolor.size(2) == 3, "dL_dcolor must be [H, W, 3]");
+    TORCH_CHECK(!dL_ddepth_map.defined() || ro.depth_map.defined(),
+                "dL_ddepth_map needs a render with the depth map (render(..., want_depth_map = true))");
+    const bool depth_grads = dL_ddepth_map.defined() || dL_dalpha.defined();
     const int64_t n = model.positions.size(0);
     BackwardOutput o;
     if (n == 0) {                                                                                     // rasterizer.cpp:130-139
@@ -493,7 +548,8 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
     if (zeroed.defined() && (zeroed.dim() != 2 || zeroed.size(0) != n)) zeroed = torch::Tensor();
     auto rb = rasterize_backward(dL_dcolor, ro.means_2d, ro.cov_2d_inv, ro.rgb, ro.opacities_act, ro.tile_ranges,
                                  ro.gaussian_indices, ro.final_T, ro.n_contrib, camera.width, camera.height,
-                                 settings.background, static_cast<int>(n), packed, /*unpack=*/false, zeroed, ro.tile_order);
+                                 settings.background, static_cast<int>(n), packed, /*unpack=*/false, zeroed, ro.tile_order,
+                                 depth_grads ? ro.depths : torch::Tensor(), dL_ddepth_map, dL_dalpha);
     o.dL_dmeans_2d = torch::empty({n, 2}, fopt(dL_dcolor));
     if (fused) {                                                // a8 + a9 + a11 in one launch, parameters updated in place
         const auto& pr = fused->params();

@@ -30,10 +30,14 @@ struct SortingOutput {             // rasterizer/sorting.hpp:18-24
     int total_pairs = 0;
     torch::Tensor tile_order;      // [tiles,4] int32, optional (not in the reference): {tile, first, end, 0}, longest list first (cugs_tile_order)
 };
-struct ForwardOutput { torch::Tensor color, final_T, n_contrib; };
+struct ForwardOutput {
+    torch::Tensor color, final_T, n_contrib;
+    torch::Tensor depth_map;       // [H,W] with rasterize_forward(..., depths) (not in the reference)
+};
 struct RasterizeBackwardOutput {
     torch::Tensor dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv;
     torch::Tensor grad_accum;      // [N,16] packed rows (not in the reference)
+    torch::Tensor dL_ddepths;      // [N] dL/dz of the depth map (rasterize_backward(..., depths, ...), unpacked)
 };
 struct ProjectionBackwardOutput { torch::Tensor dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs; };
 
@@ -53,6 +57,9 @@ struct RenderOutput {              // rasterizer/rasterizer.hpp:27-46
     mutable torch::Tensor zeroed_accum;
     std::shared_ptr<std::atomic<bool>> accum_used;
     torch::Tensor tile_order;      // [tiles,4] int32: the order the blend kernels' workgroups take the tiles in (undefined: spatial)
+    // render(..., want_depth_map = true) (not in the reference): [H,W] sum_i z_i alpha_i T_i, background 0.
+    // The alpha (coverage) map is 1 - final_T; depth_map / alpha is the normalised depth.
+    torch::Tensor depth_map;
 };
 struct BackwardOutput { torch::Tensor dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs, dL_dmeans_2d; };
 
@@ -67,7 +74,7 @@ ForwardOutput rasterize_forward(const torch::Tensor& means_2d, const torch::Tens
                                 const torch::Tensor& tile_ranges, const torch::Tensor& gaussian_indices,
                                 int img_w, int img_h, const float background[3],
                                 const torch::Tensor& packed = {}, const torch::Tensor& zero_buf = {},
-                                const torch::Tensor& tile_order = {});
+                                const torch::Tensor& tile_order = {}, const torch::Tensor& depths = {});
 // the tiles ordered by the length of their lists, longest first, from any valid tile_ranges (cugs_tile_order)
 torch::Tensor tile_order_of(const torch::Tensor& tile_ranges, int img_w, int img_h);
 RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const torch::Tensor& means_2d,
@@ -77,7 +84,9 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
                                            const torch::Tensor& n_contrib, int img_w, int img_h,
                                            const float background[3], int n_gaussians,
                                            const torch::Tensor& packed = {}, bool unpack = true,
-                                           const torch::Tensor& zeroed_accum = {}, const torch::Tensor& tile_order = {});
+                                           const torch::Tensor& zeroed_accum = {}, const torch::Tensor& tile_order = {},
+                                           const torch::Tensor& depths = {}, const torch::Tensor& dL_ddepth_map = {},
+                                           const torch::Tensor& dL_dalpha = {});
 ProjectionBackwardOutput project_backward(const torch::Tensor& dL_dmeans_2d, const torch::Tensor& dL_dcov_2d_inv,
                                           const torch::Tensor& dL_drgb, const torch::Tensor& dL_dopacity_act,
                                           const torch::Tensor& positions, const torch::Tensor& rotations,
@@ -90,8 +99,10 @@ torch::Tensor evaluate_sh_backward_cuda(int degree, const torch::Tensor& sh_coef
                                         const torch::Tensor& dL_dcolor);
 
 // `for_backward` = false (evaluation, viewer; not in the reference): no accumulator is prepared for a backward pass.
+// `want_depth_map` (not in the reference): also RenderOutput::depth_map (cugs_rasterize_forward_depth); the colour
+// outputs are unchanged, bit for bit.
 RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
-                    bool for_backward = true);
+                    bool for_backward = true, bool want_depth_map = false);
 class FusedAdam;
 class MCMCController;
 // `fused` (optional, not in the reference; single-GPU training): the projection backward applies the optimizer step to
@@ -99,10 +110,13 @@ class MCMCController;
 // in the result; dL_dmeans_2d is returned) - bit for bit render_backward + apply_gradients + step.
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& render_out,
                                const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
-                               FusedAdam* fused = nullptr, const MCMCController* mcmc = nullptr, int step = 0);
+                               FusedAdam* fused = nullptr, const MCMCController* mcmc = nullptr, int step = 0,
+                               const torch::Tensor& dL_ddepth_map = {}, const torch::Tensor& dL_dalpha = {});
 // `mcmc` (with `fused` only): the regulariser gradient and the position noise of iteration `step` ride in
 // the same launch (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + compute_regularization's
 // gradients, apply_gradients, step, inject_noise(model, step).
+// `dL_ddepth_map`, `dL_dalpha` ([H,W] each, optional, not in the reference): the gradients of RenderOutput::depth_map
+// (needs render(..., want_depth_map = true)) and of the alpha map 1 - final_T, on every route above.
 
 // training/loss.hpp:21-52 + the autograd step of trainer.cpp:214-217 in two launches.
 // Scalars are 0-dim device tensors, as in the reference.

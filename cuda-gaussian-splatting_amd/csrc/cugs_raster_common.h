@@ -39,8 +39,11 @@ struct RasterSrc {
 // Stage list entry `li` (if < end) into LDS slot threadIdx.x.  The LDS copy of the record carries the
 // Gaussian index (as bits) in its spare word 7, so that the backward's scatter address comes
 // with the same 16-byte read as the opacity.  Returns the Gaussian index (or -1).
-template <bool PACKED>
-__device__ __forceinline__ int stage_record(const RasterSrc& s, int li, int end, float4* s_rec) {
+// DEPTH (depth-map kernels): word 9 of the LDS copy - 0 in the colour chunk (r, 0, g, b) - takes
+// depths[g], so that (r, z) is an aligned pair next to (g, b).  The packed HBM record is not changed.
+template <bool PACKED, bool DEPTH = false>
+__device__ __forceinline__ int stage_record(const RasterSrc& s, int li, int end, float4* s_rec,
+                                            const float* __restrict__ depths = nullptr) {
     if (li >= end) return -1;
     const int g = s.gidx[li];
     float4 r0, r1, r2;
@@ -54,6 +57,7 @@ __device__ __forceinline__ int stage_record(const RasterSrc& s, int li, int end,
         r2 = make_float4(s.rgb[g * 3 + 0], 0.0f, s.rgb[g * 3 + 1], s.rgb[g * 3 + 2]);
     }
     r1.w = __int_as_float(g);
+    if (DEPTH) r2.y = depths[g];
     s_rec[threadIdx.x * CUGS_REC_F4 + 0] = r0;
     s_rec[threadIdx.x * CUGS_REC_F4 + 1] = r1;
     s_rec[threadIdx.x * CUGS_REC_F4 + 2] = r2;
@@ -284,6 +288,14 @@ __device__ __forceinline__ int reduce9r16_slot(int lane) {
     return -1;
 }
 
+// the two in-bank stages (selects on lane bits 1, 0) shared by reduce9r16 and reduce10r16
+__device__ __forceinline__ float reduce_r16_tail(float b0, float b1, float b2, int lane) {
+    const bool s1 = (lane & 2) != 0, s0 = (lane & 1) != 0;
+    const float c0 = xchg_add<0x4E>(s1, b0, b1);                   // quad_perm [2,3,0,1]
+    const float c1 = b2 + dpp_mov<0x4E>(b2);
+    return xchg_add<0xB1>(s0, c0, c1);                             // quad_perm [1,0,3,2]
+}
+
 __device__ __forceinline__ float reduce9r16(float cA, float cB, float v2, float v3, float v4, float v5, float v6,
                                             float v8, float v7, int lane) {
     float a0, a1, a2, a3, a4, b0, b1, b2;
@@ -305,8 +317,39 @@ __device__ __forceinline__ float reduce9r16(float cA, float cB, float v2, float 
         "s_nop 1\n\t"                                                               // the compiler's DPP reads b1 next
         : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(b0), "=&v"(b1), "=&v"(b2)
         : "v"(cA), "v"(cB), "v"(v2), "v"(v3), "v"(v4), "v"(v5), "v"(v6), "v"(v8), "v"(v7));
-    const bool s1 = (lane & 2) != 0, s0 = (lane & 1) != 0;
-    const float c0 = xchg_add<0x4E>(s1, b0, b1);                   // quad_perm [2,3,0,1]
-    const float c1 = b2 + dpp_mov<0x4E>(b2);
-    return xchg_add<0xB1>(s0, c0, c1);                             // quad_perm [1,0,3,2]
+    return reduce_r16_tail(b0, b1, b2, lane);
+}
+
+// reduce10r16: reduce9r16 with a TENTH value v9 (the depth-map backward's sum of weight * dL/dD).  Stage 1's a4 = v7
+// uses no bank selection in reduce9r16 - both halves of a row carry v7 - so it takes v7 | v9 with bank masks 0x3 / 0xc
+// (one more DPP add) and everything after it is unchanged: the v7 total lands in lanes r = 1 and 5 of the row as
+// before, the v9 total in lanes r = 9 and 13.
+// Result, per row: as reduce9r16 plus r = 9 -> slot 9 (reduce10r16_slot).
+__device__ __forceinline__ int reduce10r16_slot(int lane) {
+    return ((lane & 15) == 9) ? 9 : reduce9r16_slot(lane);
+}
+
+__device__ __forceinline__ float reduce10r16(float cA, float cB, float v2, float v3, float v4, float v5, float v6,
+                                             float v8, float v7, float v9, int lane) {
+    float a0, a1, a2, a3, a4, b0, b1, b2;
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %9, %8 row_mirror row_mask:0xf bank_mask:0xf\n\t"        // a0 = cA + mirror(cB)
+        "v_add_f32_dpp %1, %10, %10 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a1 = v2 | v3
+        "v_add_f32_dpp %1, %11, %11 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %2, %12, %12 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a2 = v4 | v5
+        "v_add_f32_dpp %2, %13, %13 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %3, %14, %14 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a3 = v6 | v8
+        "v_add_f32_dpp %3, %15, %15 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %4, %16, %16 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a4 = v7 | v9
+        "v_add_f32_dpp %4, %17, %17 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %5, %0, %0 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   // b0 = a0 | a1
+        "v_add_f32_dpp %5, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %7, %4, %4 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"   // b2 = a4 (v7 | v9 per half)
+        "v_add_f32_dpp %6, %2, %2 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   // b1 = a2 | a3
+        "v_add_f32_dpp %6, %3, %3 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "s_nop 1\n\t"                                                               // the compiler's DPP reads b1 next
+        : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(b0), "=&v"(b1), "=&v"(b2)
+        : "v"(cA), "v"(cB), "v"(v2), "v"(v3), "v"(v4), "v"(v5), "v"(v6), "v"(v8), "v"(v7), "v"(v9));
+    return reduce_r16_tail(b0, b1, b2, lane);
 }

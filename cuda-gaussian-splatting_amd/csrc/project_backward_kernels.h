@@ -336,6 +336,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
     float g_mx = 0.0f, g_my = 0.0f, g_opa = 0.0f;
     Sym2 g_inv{0.0f, 0.0f, 0.0f};
     GradMoments mom{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};            // grad_accum rows carry moments (raster_backward.hip)
+    float g_z = 0.0f;                                         // row word 9: dL/dz of the depth map (0 without one)
     const bool from_rows = (p.grad_accum != nullptr);         // kernel-uniform
     // FACTORS: the geometry inputs are requested here, with everything else the thread reads, so that the kernel pays one
     // memory round trip and not a second one behind the gradient rows (same values, same arithmetic further down)
@@ -355,7 +356,9 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
             const float4* row = reinterpret_cast<const float4*>(p.grad_accum + idx * CUGS_GRAD_STRIDE);
             const float4 r0 = row[0], r1 = row[1];
             g_rgb[0] = r0.x; g_rgb[1] = r0.y; g_rgb[2] = r0.z; g_opa = r0.w;
-            mom = GradMoments{r1.x, r1.y, r1.z, r1.w, p.grad_accum[idx * CUGS_GRAD_STRIDE + 8]};
+            const float2 r2 = *reinterpret_cast<const float2*>(p.grad_accum + idx * CUGS_GRAD_STRIDE + 8);   // words 8, 9
+            mom = GradMoments{r1.x, r1.y, r1.z, r1.w, r2.x};
+            g_z = r2.y;
         } else {
             g_rgb[0] = p.g_rgb[idx * 3 + 0]; g_rgb[1] = p.g_rgb[idx * 3 + 1]; g_rgb[2] = p.g_rgb[idx * 3 + 2];
             g_opa = p.g_opa[idx];
@@ -450,6 +453,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
             dt.y += g_my * cam.fy * J.tz_inv;
             dt.z += g_mx * (-cam.fx * t.x * J.tz_inv2) + g_my * (-cam.fy * t.y * J.tz_inv2);
             add_grad_t_from_cov(g_cov, S, W, t, cam.fx, cam.fy, J, T, dt);
+            dt.z = (g_z != 0.0f) ? dt.z + g_z : dt.z;           // depth map: z = t.z; a zero word leaves every bit
             d_pos.x = W.m00 * dt.x + W.m10 * dt.y + W.m20 * dt.z;
             d_pos.y = W.m01 * dt.x + W.m11 * dt.y + W.m21 * dt.z;
             d_pos.z = W.m02 * dt.x + W.m12 * dt.y + W.m22 * dt.z;

@@ -28,6 +28,11 @@
 //     (k_project_backward / k_unpack_grads).  Accumulator row: {drgb[3], dopa, M1x, M1y, M2xx, M2xy, M2yy};
 //   * T *= rcp(1 - al) needs no "did it contribute" select: v_rcp_f32(1.0f) is exactly 1.0f
 //     (tests/test_gpu_reduce9.py checks it on the device).
+// DEPTH (cugs_rasterize_backward_depth): the depth map is a colour channel with c = z (record word 9)
+// and background 0, the alpha map 1 - final_T one with c = 1 and background 0.  dL/dD joins the per-step dot product
+// (G += dL/dD z: one FMA) and phase 2 forms a TENTH sum, sum weight * dL/dD = dL/dz, delivered to word 9 of the row by
+// reduce10r16.  dL/dA needs no per-step work: sum_i alpha_i T_i + final_T = 1, so the channel (c = 1, bg = 0) has the
+// gradient of (c = 0, bg = -1), which only enters D's starting value (D -= final_T dL/dA).
 // The summation order differs from any sequential order; the oracle accumulates in fp64.
 // Per-contribution VALUES (not decisions) use v_rcp_f32 and fused multiply-adds: 1 ulp-level
 // differences from the oracle's divisions, far inside the 1e-4 bar.
@@ -60,12 +65,16 @@ namespace {
 
 // WIDE: accumulator larger than 4 GiB (n > 2^26 rows): 64-bit scatter addresses.
 // STATS (dev builds only): step counters written to accumulator row `stats_row` (tools/ablate_backward.py).
-template <bool PACKED, bool WIDE, bool STATS>
+// DEPTH: the depth / alpha maps' gradients too (dL_ddepth_map, dL_dalpha: [H,W], either may be NULL = zero).
+template <bool PACKED, bool WIDE, bool STATS, bool DEPTH = false>
 __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, RasterSrc src,
                                                                 const float* __restrict__ dL_dcolor,
                                                                 const float* __restrict__ final_T,
                                                                 const int32_t* __restrict__ n_contrib,
-                                                                float* __restrict__ grad_accum, int64_t stats_row) {
+                                                                float* __restrict__ grad_accum, int64_t stats_row,
+                                                                const float* __restrict__ depths,
+                                                                const float* __restrict__ dL_ddepth_map,
+                                                                const float* __restrict__ dL_dalpha) {
     // LDS budget: 12288 B of records + 8192 B of contributions = 20480 B = 1/8 of a CU's 160 KB, so EIGHT workgroups
     // (32 waves, the CU's limit) are resident instead of the seven that 20.8 KB allowed (round 2: 16 bytes of padding
     // per contribution block, 64 + 16 bytes of hit-record and vote words).  The record index of each pending Gaussian
@@ -110,29 +119,33 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
         dC1 = dL_dcolor[pix * 3 + 1];
         dC2 = dL_dcolor[pix * 3 + 2];
     }
+    float dDp = 0.0f;                                            // DEPTH: this pixel's dL/dD
+    if (DEPTH && inside && dL_ddepth_map) dDp = dL_ddepth_map[pix];
     // ---- phase-2 constants: this lane's Gaussian slot h and its four pixels (row gy, columns gx0 .. gx0+3)
     const int h2 = lane >> 4, g2i = lane & 15;
     const int gx0 = quad_x + (g2i & 1) * 4, gy = quad_y + (g2i >> 1);
     const float px2 = (float)gx0 + 0.5f, py2 = (float)gy + 0.5f;
     // reduce9r16 takes its first pair swizzled: red in lanes with bit 3 clear, green in the others
     const bool side = (lane & 8) != 0;
-    float eA[4], eB[4], e2[4];
+    float eA[4], eB[4], e2[4], eZ[4];                        // eZ: DEPTH only, the four pixels' dL/dD
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        float r = 0.0f, gg = 0.0f, bb = 0.0f;
+        float r = 0.0f, gg = 0.0f, bb = 0.0f, zz = 0.0f;
         if (gx0 + i < geo.width && gy < geo.height) {
-            const int q = (gy * geo.width + gx0 + i) * 3;
+            const int pq = gy * geo.width + gx0 + i, q = pq * 3;
             r = dL_dcolor[q + 0]; gg = dL_dcolor[q + 1]; bb = dL_dcolor[q + 2];
+            if (DEPTH && dL_ddepth_map) zz = dL_ddepth_map[pq];
         }
-        eA[i] = side ? gg : r; eB[i] = side ? r : gg; e2[i] = bb;
+        eA[i] = side ? gg : r; eB[i] = side ? r : gg; e2[i] = bb; eZ[i] = zz;
     }
-    const int slot2 = reduce9r16_slot(lane);
+    const int slot2 = DEPTH ? reduce10r16_slot(lane) : reduce9r16_slot(lane);
     const unsigned slot_off = (unsigned)(slot2 < 0 ? 0 : slot2) * 4u;
     unsigned long long hitrecs = 0ull;                       // record (float4) index of pending Gaussian h in bits [16h, 16h+16);
                                                              // stale slots of a partial flush stay valid indices
 
     // D = sum_c dL/dC_c * (colour accumulated behind the current Gaussian), starting from the background
     float D = fmaf(dC2, T * geo.bg2, fmaf(dC1, T * geo.bg1, dC0 * (T * geo.bg0)));      // backward.cu:83-87
+    if (DEPTH && inside && dL_dalpha) D = fmaf(-T, dL_dalpha[pix], D);    // the alpha map: channel (c = 0, bg = -1)
     // rem = n_contrib - (passing Gaussians seen so far, counted from the END: Q1).  A pixel stops - without
     // contributing - at the passer that takes rem below zero (backward.cu:141-145); a pixel with
     // n_contrib == 0, or outside the image, starts out finished.  open == sat(rem + 1) throughout.
@@ -164,7 +177,14 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
         const float oA = tail.y * A;
         M1 *= tail.y; Mxx *= tail.y;
         const float M1y = dy * oA, Myy = dy * M1y, Mxy = dy * M1;
-        const float total = reduce9r16(RA, RB, R2, A, M1, M1y, Mxx, Myy, Mxy, lane);
+        float total;
+        if (DEPTH) {
+            float RZ = p01.x * eZ[0];
+            RZ = fmaf(p01.z, eZ[1], RZ); RZ = fmaf(p23.x, eZ[2], RZ); RZ = fmaf(p23.z, eZ[3], RZ);
+            total = reduce10r16(RA, RB, R2, A, M1, M1y, Mxx, Myy, Mxy, RZ, lane);
+        } else {
+            total = reduce9r16(RA, RB, R2, A, M1, M1y, Mxx, Myy, Mxy, lane);
+        }
         if (slot2 >= 0 && h2 < cnt && !no_atomics) {
             const int g = __float_as_int(tail.w);
             if (WIDE) {
@@ -184,7 +204,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
         __syncthreads();
         if (s_contrib[0][0][0].x * s_contrib[1][0][0].x * s_contrib[2][0][0].x * s_contrib[3][0][0].x != 0.0f) break;
 
-        stage_record<PACKED>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec);
+        stage_record<PACKED, DEPTH>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec, depths);
         __syncthreads();
 
         if (STATS && !wave_done) ++st_batches;
@@ -224,7 +244,8 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
                     const float rcp = __builtin_amdgcn_rcpf(1.0f - al);    // al <= 0.99; rcp(1) == 1 exactly
                     T *= rcp;                                              // T_before = T_after / (1 - alpha)
                     const float weight = al * T;
-                    const float G = fmaf(dC2, col.w, fmaf(dC1, col.z, dC0 * col.x));
+                    float G = fmaf(dC2, col.w, fmaf(dC1, col.z, dC0 * col.x));
+                    if (DEPTH) G = fmaf(dDp, col.y, G);                    // + dL/dD z (record word 9)
                     const float gate = fmaf(T, G, -(rcp * D)) * gk;        // dL/dalpha, gated
                     D = fmaf(weight, G, D);
                     if (STATS) {
@@ -257,19 +278,28 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
 
 // grad_accum rows -> the four reference-layout tensors of RasterizeBackwardOutput (backward.hpp); applies the
 // per-Gaussian map from the accumulated moments (see the header comment) with Sigma'^-1 = (a, b, c).
-template <bool PACKED>
+// DEPTH: also dL_ddepths [n] from word 9.
+template <bool PACKED, bool DEPTH = false>
 __global__ __launch_bounds__(CUGS_BLOCK) void k_unpack_grads(int64_t n, const float* __restrict__ acc,
                                                              const float* __restrict__ packed,
                                                              const float* __restrict__ cov_2d_inv,
                                                              float* __restrict__ dL_drgb,
                                                              float* __restrict__ dL_dopa,
                                                              float* __restrict__ dL_dmeans,
-                                                             float* __restrict__ dL_dcov) {
+                                                             float* __restrict__ dL_dcov,
+                                                             float* __restrict__ dL_ddepths) {
     const int64_t i = (int64_t)blockIdx.x * CUGS_BLOCK + threadIdx.x;
     if (i >= n) return;
     const float4* row = reinterpret_cast<const float4*>(acc + i * CUGS_GRAD_STRIDE);
     const float4 r0 = row[0], r1 = row[1];
-    const float r2 = acc[i * CUGS_GRAD_STRIDE + 8];
+    float r2;
+    if (DEPTH) {
+        const float2 w89 = *reinterpret_cast<const float2*>(acc + i * CUGS_GRAD_STRIDE + 8);
+        r2 = w89.x;
+        dL_ddepths[i] = w89.y;
+    } else {
+        r2 = acc[i * CUGS_GRAD_STRIDE + 8];
+    }
     float a, b, c;
     if (PACKED) {
         const float4* rec = reinterpret_cast<const float4*>(packed + i * CUGS_PACKED_STRIDE);
@@ -296,7 +326,10 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
                                        const float* dL_dcolor, const float* final_T,
                                        const int32_t* n_contrib, int64_t n, float* grad_accum,
                                        float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                       float* dL_dcov_2d_inv, bool prezeroed, const uint32_t* tile_order, void* stream) {
+                                       float* dL_dcov_2d_inv, bool prezeroed, const uint32_t* tile_order, void* stream,
+                                       bool depth_map = false, const float* depths = nullptr,
+                                       const float* dL_ddepth_map = nullptr, const float* dL_dalpha = nullptr,
+                                       float* dL_ddepths = nullptr) {
     if (width < 0 || height < 0 || n < 0 || !background_host) return CUGS_EINVAL;
     if (n == 0) return 0;
     if (!grad_accum) return CUGS_EINVAL;
@@ -304,6 +337,7 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
     const int n_soa = (dL_drgb != nullptr) + (dL_dopacity_act != nullptr) + (dL_dmeans_2d != nullptr) +
                       (dL_dcov_2d_inv != nullptr);
     if (n_soa != 0 && n_soa != 4) return CUGS_EINVAL;
+    if (depth_map && (n_soa == 4) != (dL_ddepths != nullptr)) return CUGS_EINVAL;   // dL_ddepths with the four, not alone
     if (n_soa == 4 && !packed && !cov_2d_inv) return CUGS_EINVAL;
     if (packed && !cugs_aligned16(packed)) return CUGS_EALIGN;
     if (tile_order && !cugs_aligned16(tile_order)) return CUGS_EALIGN;
@@ -320,6 +354,7 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
     if (ntx > 0 && nty > 0 && gaussian_indices) {               // backward.cu:267-269; NULL indices = no pairs
         if (!tile_ranges || !dL_dcolor || !final_T || !n_contrib) return CUGS_EINVAL;
         if (!packed && (!means_2d || !cov_2d_inv || !rgb || !opacities_act)) return CUGS_EINVAL;
+        if (depth_map && !depths) return CUGS_EINVAL;
         if ((int64_t)width * height > 2147483647ll / 3) return CUGS_EOVERFLOW;
         RasterGeom geo{width, height, ntx, ntx * nty, background_host[0], background_host[1], background_host[2]};
         RasterSrc src{tile_ranges, gaussian_indices, packed, means_2d, cov_2d_inv, rgb, opacities_act, reinterpret_cast<const uint4*>(tile_order)};
@@ -330,7 +365,17 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
 #endif
 #define CUGS_LAUNCH_BWD(P, W, S)                                                                              \
     hipLaunchKernelGGL((k_raster_backward<P, W, S>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, \
-                       dL_dcolor, final_T, n_contrib, grad_accum, stats_arg)
+                       dL_dcolor, final_T, n_contrib, grad_accum, stats_arg, nullptr, nullptr, nullptr)
+#define CUGS_LAUNCH_BWD_DEPTH(P, W)                                                                                  \
+    hipLaunchKernelGGL((k_raster_backward<P, W, false, true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, \
+                       dL_dcolor, final_T, n_contrib, grad_accum, stats_arg, depths, dL_ddepth_map, dL_dalpha)
+        if (depth_map) {                                        // no step counters on this route
+            if (packed) {
+                if (wide) CUGS_LAUNCH_BWD_DEPTH(true, true); else CUGS_LAUNCH_BWD_DEPTH(true, false);
+            } else {
+                if (wide) CUGS_LAUNCH_BWD_DEPTH(false, true); else CUGS_LAUNCH_BWD_DEPTH(false, false);
+            }
+        } else
 #ifdef CUGS_DEV
         if (stats) {
             if (packed) CUGS_LAUNCH_BWD(true, true, true); else CUGS_LAUNCH_BWD(false, true, true);
@@ -342,16 +387,20 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
             if (wide) CUGS_LAUNCH_BWD(false, true, false); else CUGS_LAUNCH_BWD(false, false, false);
         }
 #undef CUGS_LAUNCH_BWD
+#undef CUGS_LAUNCH_BWD_DEPTH
         CUGS_LAUNCH_CHECK();
     }
     if (n_soa == 4) {
         const dim3 grid((unsigned)((n + CUGS_BLOCK - 1) / CUGS_BLOCK));
-        if (packed)
-            hipLaunchKernelGGL(k_unpack_grads<true>, grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed, cov_2d_inv,
-                               dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv);
-        else
-            hipLaunchKernelGGL(k_unpack_grads<false>, grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed, cov_2d_inv,
-                               dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv);
+#define CUGS_LAUNCH_UNPACK(P, D)                                                                                 \
+    hipLaunchKernelGGL((k_unpack_grads<P, D>), grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed, cov_2d_inv, \
+                       dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, dL_ddepths)
+        if (depth_map) {
+            if (packed) CUGS_LAUNCH_UNPACK(true, true); else CUGS_LAUNCH_UNPACK(false, true);
+        } else {
+            if (packed) CUGS_LAUNCH_UNPACK(true, false); else CUGS_LAUNCH_UNPACK(false, false);
+        }
+#undef CUGS_LAUNCH_UNPACK
         CUGS_LAUNCH_CHECK();
     }
     return 0;
@@ -399,6 +448,22 @@ extern "C" int cugs_rasterize_backward_ordered(int width, int height, const floa
                                    dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, prezeroed != 0, tile_order, stream);
 }
 
+extern "C" int cugs_rasterize_backward_depth(int width, int height, const float background_host[3],
+                                             const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                             const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                             const float* opacities_act, const float* packed,
+                                             const float* dL_dcolor, const float* final_T,
+                                             const int32_t* n_contrib, int64_t n, float* grad_accum,
+                                             float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                             float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
+                                             const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
+                                             float* dL_ddepths, void* stream) {
+    return rasterize_backward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
+                                   opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
+                                   dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, prezeroed != 0, tile_order, stream, true,
+                                   depths, dL_ddepth_map, dL_dalpha, dL_ddepths);
+}
+
 #ifdef CUGS_DEV
 // ---- development hooks (libcugs_hip_dev.so only; not part of include/cugs_hip.h) ------------------
 // cugsdbg_reduce9: one wave runs reduce9t on caller data.  in: [9][64] floats (value k of lane l at k*64+l,
@@ -422,6 +487,15 @@ __global__ void k_dbg_reduce9r16(const float* __restrict__ in, float* __restrict
                         in[6 * 64 + l], in[8 * 64 + l], in[7 * 64 + l], l);
     slots[l] = reduce9r16_slot(l);
 }
+// reduce10r16: in [10][64] (value k of lane l at k*64+l), out [64], slots [64]
+__global__ void k_dbg_reduce10r16(const float* __restrict__ in, float* __restrict__ out, int* __restrict__ slots) {
+    const int l = threadIdx.x;
+    const bool side = (l & 8) != 0;
+    const float v0 = in[0 * 64 + l], v1 = in[1 * 64 + l];
+    out[l] = reduce10r16(side ? v1 : v0, side ? v0 : v1, in[2 * 64 + l], in[3 * 64 + l], in[4 * 64 + l], in[5 * 64 + l],
+                         in[6 * 64 + l], in[8 * 64 + l], in[7 * 64 + l], in[9 * 64 + l], l);
+    slots[l] = reduce10r16_slot(l);
+}
 __global__ void k_dbg_rcp(const float* __restrict__ in, float* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = __builtin_amdgcn_rcpf(in[i]);
@@ -441,6 +515,11 @@ extern "C" int cugsdbg_reduce9(const float* in, float* out, int* slots, void* st
 }
 extern "C" int cugsdbg_reduce9r16(const float* in, float* out, int* slots, void* stream) {
     hipLaunchKernelGGL(k_dbg_reduce9r16, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), in, out, slots);
+    CUGS_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int cugsdbg_reduce10r16(const float* in, float* out, int* slots, void* stream) {
+    hipLaunchKernelGGL(k_dbg_reduce10r16, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), in, out, slots);
     CUGS_LAUNCH_CHECK();
     return 0;
 }

@@ -10,16 +10,22 @@
 // wave64 ballot compaction of the records each quad can see).  The inner loop is VALU-bound
 // (~35 instructions per surviving (pixel, Gaussian) evaluation); HBM traffic is the 4 B index +
 // 48 B record per (tile, Gaussian) pair plus 20 B per pixel written.
+//
+// DEPTH (cugs_rasterize_forward_depth): the accumulated depth map D = sum_i z_i alpha_i T_i is one more
+// colour channel with value z_i = depths[i] and background 0.  stage_record puts z into word 9 of the LDS record (0 in
+// the colour instantiations), so red and depth are the aligned pair (r, z) and accumulate in ONE v_pk_fma_f32, as green
+// and blue do: no extra VALU per step, and each lane's IEEE fma gives the bits of fmaf - the depth map is bit for bit
+// the red channel of a blend with rgb := z, bg := 0.
 #include "cugs_raster_common.h"
 
 namespace {
 
-template <bool PACKED>
-__global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward(RasterGeom geo, RasterSrc src,
-                                                               float* __restrict__ out_color,
-                                                               float* __restrict__ out_final_T,
-                                                               int32_t* __restrict__ out_n_contrib,
-                                                               float4* __restrict__ zero_buf, uint32_t zero_vec4) {
+// The body of both kernels below.  The depth-map kernel is a separate entry with its own parameter list, so that the
+// colour kernel's parameter block - and with it the offset of the hidden arguments it reads - stays as it was.
+template <bool PACKED, bool DEPTH>
+__device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc src, float* out_color, float* out_final_T,
+                                                    int32_t* out_n_contrib, float4* zero_buf, uint32_t zero_vec4,
+                                                    const float* depths, float* out_depth) {
     __shared__ float4 s_rec[CUGS_BLOCK * CUGS_REC_F4];
     __shared__ int s_wave_done[4];
 
@@ -58,6 +64,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward(RasterGeom geo, R
     typedef float v2f __attribute__((ext_vector_type(2)));
     float T = 1.0f, C0 = 0.0f;
     v2f C12 = {0.0f, 0.0f};                             // green/blue as one packed-fp32 accumulator (v_pk_fma_f32)
+    v2f C0Z = {0.0f, 0.0f};                             // DEPTH: red and depth likewise (record words 8, 9)
     float count = 0.0f;                                 // contributors: a float counter (exact below 2^24 per tile list)
     float open = inside ? 1.0f : 0.0f;                  // 1 while the pixel still blends, 0 once T < 1/255
     bool wave_done = (__ballot(open != 0.0f) == 0ull);
@@ -68,7 +75,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward(RasterGeom geo, R
         __syncthreads();
         if (s_wave_done[0] & s_wave_done[1] & s_wave_done[2] & s_wave_done[3]) break;
 
-        stage_record<PACKED>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec);
+        stage_record<PACKED, DEPTH>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec, depths);
         __syncthreads();
 
         if (!wave_done) {
@@ -93,7 +100,8 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward(RasterGeom geo, R
                     const float al = alpha * passf;
                     // al == 0 (skipped or finished pixel) leaves C, T and count untouched exactly
                     const float weight = al * T;
-                    C0 = fmaf(weight, col.x, C0);
+                    if (DEPTH) C0Z = __builtin_elementwise_fma((v2f){weight, weight}, (v2f){col.x, col.y}, C0Z);
+                    else C0 = fmaf(weight, col.x, C0);
                     C12 = __builtin_elementwise_fma((v2f){weight, weight}, (v2f){col.z, col.w}, C12);   // record words 10,11: an aligned pair
                     T *= (1.0f - al);
                     count += passf;
@@ -107,12 +115,39 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward(RasterGeom geo, R
 
     if (inside) {
         const int pix = py * geo.width + px;
+        if (DEPTH) {
+            C0 = C0Z.x;
+            out_depth[pix] = fmaf(T, 0.0f, C0Z.y);           // background 0, as the red channel with bg := 0
+        }
         out_color[pix * 3 + 0] = fmaf(T, geo.bg0, C0);
         out_color[pix * 3 + 1] = fmaf(T, geo.bg1, C12.x);
         out_color[pix * 3 + 2] = fmaf(T, geo.bg2, C12.y);
         out_final_T[pix] = T;
         out_n_contrib[pix] = (int)count;
     }
+}
+
+template <bool PACKED>
+__global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward(RasterGeom geo, RasterSrc src,
+                                                               float* __restrict__ out_color,
+                                                               float* __restrict__ out_final_T,
+                                                               int32_t* __restrict__ out_n_contrib,
+                                                               float4* __restrict__ zero_buf, uint32_t zero_vec4) {
+    raster_forward_tile<PACKED, false>(geo, src, out_color, out_final_T, out_n_contrib, zero_buf, zero_vec4, nullptr,
+                                       nullptr);
+}
+
+// DEPTH instantiation: also the depth map [H,W] from depths [n]
+template <bool PACKED>
+__global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward_depth(RasterGeom geo, RasterSrc src,
+                                                                     float* __restrict__ out_color,
+                                                                     float* __restrict__ out_final_T,
+                                                                     int32_t* __restrict__ out_n_contrib,
+                                                                     float4* __restrict__ zero_buf, uint32_t zero_vec4,
+                                                                     const float* __restrict__ depths,
+                                                                     float* __restrict__ out_depth) {
+    raster_forward_tile<PACKED, true>(geo, src, out_color, out_final_T, out_n_contrib, zero_buf, zero_vec4, depths,
+                                      out_depth);
 }
 
 }  // namespace
@@ -122,7 +157,8 @@ int rasterize_forward_impl(int width, int height, const float background_host[3]
                            const int32_t* gaussian_indices, const float* means_2d, const float* cov_2d_inv,
                            const float* rgb, const float* opacities_act, const float* packed, float* out_color,
                            float* out_final_T, int32_t* out_n_contrib, void* zero_buf, size_t zero_bytes,
-                           const uint32_t* tile_order, void* stream) {
+                           const uint32_t* tile_order, void* stream, bool depth_map = false,
+                           const float* depths = nullptr, float* out_depth = nullptr) {
     if (width < 0 || height < 0 || !background_host) return CUGS_EINVAL;
     if (zero_bytes && (!zero_buf || (reinterpret_cast<uintptr_t>(zero_buf) & 15u) || (zero_bytes & 15u) ||
                        zero_bytes / 16 > 0xFFFFFFFFull))
@@ -133,6 +169,7 @@ int rasterize_forward_impl(int width, int height, const float background_host[3]
         return 0;
     }
     if (!tile_ranges || !out_color || !out_final_T || !out_n_contrib) return CUGS_EINVAL;
+    if (depth_map && (!out_depth || (gaussian_indices && !depths))) return CUGS_EINVAL;
     // gaussian_indices and the per-Gaussian sources may be NULL for an empty pair list (P == 0: every
     // tile range is {0,0} and nothing is dereferenced).  With indices present a source is required.
     if (gaussian_indices && !packed && (!means_2d || !cov_2d_inv || !rgb || !opacities_act)) return CUGS_EINVAL;
@@ -144,12 +181,20 @@ int rasterize_forward_impl(int width, int height, const float background_host[3]
     hipStream_t st = static_cast<hipStream_t>(stream);
     float4* zb = zero_bytes ? static_cast<float4*>(zero_buf) : nullptr;
     const uint32_t zv = (uint32_t)(zero_bytes / 16);
-    if (packed)
+    if (depth_map) {
+        if (packed)
+            hipLaunchKernelGGL((k_raster_forward_depth<true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
+                               out_color, out_final_T, out_n_contrib, zb, zv, depths, out_depth);
+        else
+            hipLaunchKernelGGL((k_raster_forward_depth<false>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
+                               out_color, out_final_T, out_n_contrib, zb, zv, depths, out_depth);
+    } else if (packed) {
         hipLaunchKernelGGL((k_raster_forward<true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
                            out_color, out_final_T, out_n_contrib, zb, zv);
-    else
+    } else {
         hipLaunchKernelGGL((k_raster_forward<false>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
                            out_color, out_final_T, out_n_contrib, zb, zv);
+    }
     CUGS_LAUNCH_CHECK();
     return 0;
 }
@@ -183,4 +228,16 @@ extern "C" int cugs_rasterize_forward_ordered(int width, int height, const float
     return rasterize_forward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
                                   opacities_act, packed, out_color, out_final_T, out_n_contrib, zero_buf, zero_bytes, tile_order,
                                   stream);
+}
+
+extern "C" int cugs_rasterize_forward_depth(int width, int height, const float background_host[3],
+                                            const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                            const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                            const float* opacities_act, const float* packed, float* out_color,
+                                            float* out_final_T, int32_t* out_n_contrib, void* zero_buf,
+                                            size_t zero_bytes, const uint32_t* tile_order, const float* depths,
+                                            float* out_depth, void* stream) {
+    return rasterize_forward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
+                                  opacities_act, packed, out_color, out_final_T, out_n_contrib, zero_buf, zero_bytes, tile_order,
+                                  stream, true, depths, out_depth);
 }

@@ -436,20 +436,29 @@ def rasterize_forward(means_2d: torch.Tensor, cov_2d_inv: torch.Tensor, rgb: tor
                       opacities: torch.Tensor, tile_ranges: torch.Tensor, gaussian_indices: torch.Tensor,
                       img_w: int, img_h: int, background: Sequence[float],
                       packed: Optional[torch.Tensor] = None, zero_buf: Optional[torch.Tensor] = None,
-                      tile_order: Optional[torch.Tensor] = None) -> ForwardOutput:
+                      tile_order: Optional[torch.Tensor] = None,
+                      depths: Optional[torch.Tensor] = None) -> ForwardOutput:
     """`zero_buf` (optional, not in the reference): a contiguous float32 tensor the launch also fills with zeros -
     the accumulator of the backward blend, cleared for free by this issue-bound kernel (cugs_rasterize_forward_zero).
     `tile_order` (optional, not in the reference): [tiles, 4] int32, the order the workgroups take the tiles in
-    (tile_order_of / SortingOutput.tile_order: longest list first); the outputs do not depend on it."""
+    (tile_order_of / SortingOutput.tile_order: longest list first); the outputs do not depend on it.
+    `depths` (optional, not in the reference): the [N] depths of the projection - the blend also accumulates the depth
+    map sum_i z_i alpha_i T_i into ForwardOutput.depth_map (cugs_rasterize_forward_depth); colour, final_T and n_contrib
+    are unchanged, bit for bit."""
     _torch_check(means_2d.is_cuda, "means_2d must be on CUDA")
     dev = means_2d.device
     color = torch.empty((img_h, img_w, 3), dtype=torch.float32, device=dev)
     final_T = torch.empty((img_h, img_w), dtype=torch.float32, device=dev)
     n_contrib = torch.empty((img_h, img_w), dtype=torch.int32, device=dev)
+    depth_map = None
+    if depths is not None:
+        _torch_check(depths.is_cuda and depths.device == dev, "depths must be on the device of means_2d")
+        _torch_check(depths.dim() == 1 and depths.shape[0] == means_2d.shape[0], "depths must be [N]")
+        depth_map = torch.empty((img_h, img_w), dtype=torch.float32, device=dev)     # every pixel is written
     if img_w == 0 or img_h == 0:
         if zero_buf is not None:
             zero_buf.zero_()                 # the promise holds without a blend launch too (render() relies on it)
-        return ForwardOutput(color, final_T, n_contrib)
+        return ForwardOutput(color, final_T, n_contrib, depth_map)
     bg = (C.c_float * 3)(*[float(b) for b in background])
     if zero_buf is not None:
         _torch_check(zero_buf.is_contiguous() and zero_buf.dtype == torch.float32 and zero_buf.numel() % 4 == 0,
@@ -457,6 +466,17 @@ def rasterize_forward(means_2d: torch.Tensor, cov_2d_inv: torch.Tensor, rgb: tor
     if tile_order is not None:
         _torch_check(tile_order.is_contiguous() and tile_order.dtype == torch.int32 and
                      tile_order.numel() == 4 * tile_ranges.shape[0], "tile_order must be a contiguous [tiles, 4] int32 tensor")
+    if depths is not None:
+        check(lib.cugs_rasterize_forward_depth(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
+                                               _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
+                                               _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
+                                               _ptr(opacities.contiguous()), _ptr(packed), _ptr(color), _ptr(final_T),
+                                               _ptr(n_contrib), _ptr(zero_buf),
+                                               zero_buf.numel() * 4 if zero_buf is not None else 0, _ptr(tile_order),
+                                               _ptr(_f32c(depths)), _ptr(depth_map), _stream(dev)),
+              "cugs_rasterize_forward_depth")
+        return ForwardOutput(color, final_T, n_contrib, depth_map)
+    if tile_order is not None:
         check(lib.cugs_rasterize_forward_ordered(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
                                                  _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
                                                  _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
@@ -487,15 +507,30 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
                        img_w: int, img_h: int, background: Sequence[float], n_gaussians: int,
                        packed: Optional[torch.Tensor] = None, unpack: bool = True,
                        zeroed_accum: Optional[torch.Tensor] = None,
-                       tile_order: Optional[torch.Tensor] = None) -> RasterizeBackwardOutput:
+                       tile_order: Optional[torch.Tensor] = None, depths: Optional[torch.Tensor] = None,
+                       dL_ddepth_map: Optional[torch.Tensor] = None,
+                       dL_dalpha: Optional[torch.Tensor] = None) -> RasterizeBackwardOutput:
     """`zeroed_accum` (optional, not in the reference): an [N, 16] accumulator that is already all zeros (cleared by
     rasterize_forward(..., zero_buf=...)): used as is, without the fill.
     `tile_order` (optional, not in the reference): as in rasterize_forward; the sums are the same up to the order of
-    the atomic adds."""
+    the atomic adds.
+    `depths`, `dL_ddepth_map`, `dL_dalpha` (optional, not in the reference): the gradients of the depth map
+    (rasterize_forward(..., depths=...)) and of the alpha map 1 - final_T, [H,W] each, either may be None (zero);
+    `depths` is required with either (cugs_rasterize_backward_depth).  They add to the opacity and 2-D gradients; dL/dz
+    goes to word 9 of each accumulator row and, unpacked, to RasterizeBackwardOutput.dL_ddepths."""
     _torch_check(dL_dcolor.is_cuda, "dL_dcolor must be on CUDA")
     dev = dL_dcolor.device
     n = int(n_gaussians)
     f = dict(dtype=torch.float32, device=dev)
+    depth_route = depths is not None or dL_ddepth_map is not None or dL_dalpha is not None
+    if depth_route:
+        _torch_check(depths is not None, "the depth / alpha map gradients need the projection's depths")
+        _torch_check(depths.is_cuda and depths.device == dev and depths.dim() == 1 and depths.shape[0] == n,
+                     "depths must be [N] on the device of dL_dcolor")
+        for name, g in (("dL_ddepth_map", dL_ddepth_map), ("dL_dalpha", dL_dalpha)):
+            if g is not None:
+                _torch_check(g.is_cuda and g.device == dev, f"{name} must be on the device of dL_dcolor")
+                _torch_check(tuple(g.shape) == (int(img_h), int(img_w)), f"{name} must be [H, W] = [{img_h}, {img_w}]")
     if zeroed_accum is not None:
         _torch_check(tuple(zeroed_accum.shape) == (n, _lib.GRAD_STRIDE) and zeroed_accum.is_contiguous(),
                      "zeroed_accum must be a contiguous [N, 16] float32 tensor")
@@ -506,9 +541,24 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
         d_means, d_cov = torch.empty((n, 2), **f), torch.empty((n, 3), **f)
     else:
         d_rgb = d_opa = d_means = d_cov = None
+    d_z = torch.empty((n,), **f) if unpack and depth_route else None
     if n > 0 and tile_order is not None:
         _torch_check(tile_order.is_contiguous() and tile_order.dtype == torch.int32 and
                      tile_order.numel() == 4 * tile_ranges.shape[0], "tile_order must be a contiguous [tiles, 4] int32 tensor")
+    if n > 0 and depth_route:
+        bg = (C.c_float * 3)(*[float(b) for b in background])
+        f32 = lambda t: None if t is None else _f32c(t)
+        check(lib.cugs_rasterize_backward_depth(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
+                                                _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
+                                                _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
+                                                _ptr(opacities.contiguous()), _ptr(packed),
+                                                _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
+                                                _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
+                                                _ptr(d_means), _ptr(d_cov), 1 if zeroed_accum is not None else 0,
+                                                _ptr(tile_order), _ptr(_f32c(depths)), _ptr(f32(dL_ddepth_map)),
+                                                _ptr(f32(dL_dalpha)), _ptr(d_z), _stream(dev)),
+              "cugs_rasterize_backward_depth")
+    elif n > 0 and tile_order is not None:
         bg = (C.c_float * 3)(*[float(b) for b in background])
         check(lib.cugs_rasterize_backward_ordered(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
                                                   _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
@@ -527,7 +577,7 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
                                           _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
                                           _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
                                           _ptr(d_means), _ptr(d_cov), _stream(dev)), "cugs_rasterize_backward")
-    return RasterizeBackwardOutput(d_rgb, d_opa, d_means, d_cov, accum)
+    return RasterizeBackwardOutput(d_rgb, d_opa, d_means, d_cov, accum, dL_ddepths=d_z)
 
 
 def project_backward(dL_dmeans_2d: Optional[torch.Tensor], dL_dcov_2d_inv: Optional[torch.Tensor],
@@ -622,12 +672,15 @@ OVERLAP_COLOUR = False     # render(): the projection's colour half on a side st
 
 
 def render(model: GaussianModel, camera: CameraInfo, settings: RenderSettings, for_backward: bool = True,
-           defer_count: bool = False) -> RenderOutput:
+           defer_count: bool = False, want_depth_map: bool = False) -> RenderOutput:
     """`for_backward=False` (evaluation, viewer): skips preparing the backward's accumulator (64 B/Gaussian).
     `defer_count=True` (training loops; not in the reference): returns without waiting for the sort's pair count, so
     the caller can queue the loss behind the forward blend before the host blocks; `RenderOutput.wait()` - called by
     render_backward - completes it (`total_pairs`, the trimmed `gaussian_indices`) and raises PredictionMiss if the
-    predicted capacity was too small (the view must then be rendered again: the image is invalid)."""
+    predicted capacity was too small (the view must then be rendered again: the image is invalid).
+    `want_depth_map=True` (not in the reference): the blend also accumulates RenderOutput.depth_map [H,W]
+    = sum_i z_i alpha_i T_i (background 0) - colour, final_T and n_contrib are unchanged, bit for bit; with it
+    render_backward takes dL_ddepth_map.  RenderOutput.alpha = 1 - final_T is there either way."""
     _torch_check(model.is_valid(), "GaussianModel is not valid")
     _torch_check(model.positions.is_cuda, "GaussianModel must be on CUDA device")
     n = model.num_gaussians()
@@ -642,7 +695,8 @@ def render(model: GaussianModel, camera: CameraInfo, settings: RenderSettings, f
                             torch.zeros((camera.height, camera.width), **i), torch.empty((0, 2), **f),
                             torch.empty((0,), **f), torch.empty((0, 3), **f), torch.empty((0,), **i),
                             torch.empty((0, 3), **f), torch.empty((0,), **f), torch.empty((0,), **i),
-                            torch.empty((0, 2), **i))
+                            torch.empty((0, 2), **i),
+                            depth_map=torch.zeros((camera.height, camera.width), **f) if want_depth_map else None)
     active_degree = min(int(settings.active_sh_degree), model.max_sh_degree())
     proj = project_gaussians(model.positions, model.rotations, model.scales, model.opacities, model.sh_coeffs,
                              camera, active_degree, settings.scale_modifier, want_colour_gate=for_backward,
@@ -652,7 +706,8 @@ def render(model: GaussianModel, camera: CameraInfo, settings: RenderSettings, f
     accum = torch.empty((n, _lib.GRAD_STRIDE), **f) if for_backward else None
     blend = lambda s: rasterize_forward(proj.means_2d, proj.cov_2d_inv, proj.rgb, proj.opacities_act, s.tile_ranges,
                                         s.gaussian_values_sorted, camera.width, camera.height, settings.background,
-                                        packed=proj.packed, zero_buf=accum, tile_order=s.tile_order)
+                                        packed=proj.packed, zero_buf=accum, tile_order=s.tile_order,
+                                        depths=proj.depths if want_depth_map else None)
     srt = sort_gaussians_predicted(proj.means_2d, proj.depths, proj.radii, proj.tiles_touched, camera.width,
                                    camera.height, want_keys=False, keyed_workspace=proj.sort_workspace,
                                    want_tile_order=wants_tile_order(dev))
@@ -662,7 +717,7 @@ def render(model: GaussianModel, camera: CameraInfo, settings: RenderSettings, f
         return RenderOutput(fwd.color, fwd.final_T, fwd.n_contrib, proj.means_2d, proj.depths, proj.cov_2d_inv,
                             proj.radii, proj.rgb, proj.opacities_act, srt.gaussian_values_sorted, srt.tile_ranges,
                             packed=proj.packed, colour_gate=proj.colour_gate, total_pairs=-1, zeroed_accum=accum,
-                            pending=srt, tile_order=srt.tile_order)
+                            pending=srt, tile_order=srt.tile_order, depth_map=fwd.depth_map)
     if isinstance(srt, PendingSort):
         srt, valid = srt.finish()
         if not valid:                                    # prediction too small (e.g. right after densification)
@@ -670,14 +725,16 @@ def render(model: GaussianModel, camera: CameraInfo, settings: RenderSettings, f
     return RenderOutput(fwd.color, fwd.final_T, fwd.n_contrib, proj.means_2d, proj.depths, proj.cov_2d_inv,
                         proj.radii, proj.rgb, proj.opacities_act, srt.gaussian_values_sorted, srt.tile_ranges,
                         packed=proj.packed, colour_gate=proj.colour_gate, total_pairs=srt.total_pairs,
-                        zeroed_accum=accum, tile_order=srt.tile_order)
+                        zeroed_accum=accum, tile_order=srt.tile_order, depth_map=fwd.depth_map)
 
 
 def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: GaussianModel,
                     camera: CameraInfo, settings: RenderSettings,
                     dL_drgb_gated_out: Optional[torch.Tensor] = None,
                     geom_flat: Optional[torch.Tensor] = None, fused_adam=None, on_gated_ready=None,
-                    mcmc=None, mcmc_step: int = 0, mcmc_noise: Optional[torch.Tensor] = None) -> BackwardOutput:
+                    mcmc=None, mcmc_step: int = 0, mcmc_noise: Optional[torch.Tensor] = None,
+                    dL_ddepth_map: Optional[torch.Tensor] = None,
+                    dL_dalpha: Optional[torch.Tensor] = None) -> BackwardOutput:
     """`dL_drgb_gated_out` ([N,3], optional, not in the reference): when given, the per-view SH gradient
     is NOT materialised (dL_dsh_coeffs is None) and the gated colour gradient is written there instead,
     for parallel.exchange_gradients() to rebuild the summed SH gradient after the all-gather.
@@ -690,9 +747,26 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
     Equivalent, bit for bit, to render_backward + apply_gradients + step.
     `mcmc` (an MCMCController, with fused_adam only): the per-iteration MCMC work rides in the same launch
     (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + the gradients of
-    mcmc.compute_regularization, apply_gradients, step, mcmc.inject_noise(model, mcmc_step, mcmc_noise)."""
+    mcmc.compute_regularization, apply_gradients, step, mcmc.inject_noise(model, mcmc_step, mcmc_noise).
+    `dL_ddepth_map`, `dL_dalpha` ([H,W] each, optional, not in the reference): the gradients of
+    RenderOutput.depth_map (needs render(..., want_depth_map=True)) and of RenderOutput.alpha.  They reach the
+    parameters through the blend (opacity, 2-D mean and covariance) and, for the depth map, through z = t.z
+    (dL_dpositions += dL/dz W[2,:]); never the SH coefficients.  Plain and fused (fused_adam, mcmc) routes; the
+    data-parallel arguments are refused with them."""
     _torch_check(dL_dcolor.is_cuda, "dL_dcolor must be on CUDA device")
     _torch_check(dL_dcolor.dim() == 3 and dL_dcolor.shape[2] == 3, "dL_dcolor must be [H, W, 3]")
+    depth_grads = dL_ddepth_map is not None or dL_dalpha is not None
+    if depth_grads:
+        _torch_check(dL_ddepth_map is None or render_out.depth_map is not None,
+                     "dL_ddepth_map needs a render with the depth map (render(..., want_depth_map=True))")
+        hw = (int(dL_dcolor.shape[0]), int(dL_dcolor.shape[1]))
+        for name, g in (("dL_ddepth_map", dL_ddepth_map), ("dL_dalpha", dL_dalpha)):
+            if g is not None:
+                _torch_check(g.is_cuda and g.device == dL_dcolor.device, f"{name} must be on the device of dL_dcolor")
+                _torch_check(tuple(g.shape) == hw, f"{name} must be [H, W] = [{hw[0]}, {hw[1]}]")
+        _torch_check(dL_drgb_gated_out is None and geom_flat is None and on_gated_ready is None,
+                     "the depth / alpha map gradients are not supported with the data-parallel gradient exchange "
+                     "(dL_drgb_gated_out, geom_flat, on_gated_ready)")
     n = model.num_gaussians()
     dev = dL_dcolor.device
     f = dict(dtype=torch.float32, device=dev)
@@ -714,7 +788,9 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                             render_out.opacities_act, render_out.tile_ranges, render_out.gaussian_indices,
                             render_out.final_T, render_out.n_contrib, camera.width, camera.height,
                             settings.background, n, packed=render_out.packed, unpack=False, zeroed_accum=zeroed,
-                            tile_order=getattr(render_out, "tile_order", None))
+                            tile_order=getattr(render_out, "tile_order", None),
+                            depths=render_out.depths if depth_grads else None, dL_ddepth_map=dL_ddepth_map,
+                            dL_dalpha=dL_dalpha)
     d_means_2d = torch.empty((n, 2), **f)
     if fused_adam is not None:
         _torch_check(fused_adam.model_ is model, "fused_adam must have been built on this model")

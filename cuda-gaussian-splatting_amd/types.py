@@ -163,6 +163,7 @@ class ForwardOutput:
     color: torch.Tensor
     final_T: torch.Tensor
     n_contrib: torch.Tensor
+    depth_map: Optional[torch.Tensor] = None    # [H,W] (rasterize_forward(..., depths=...); not in the reference)
 
 
 @dataclass
@@ -172,6 +173,7 @@ class RasterizeBackwardOutput:
     dL_dmeans_2d: torch.Tensor
     dL_dcov_2d_inv: torch.Tensor
     grad_accum: Optional[torch.Tensor] = None   # [N,16] packed rows (not in the reference)
+    dL_ddepths: Optional[torch.Tensor] = None   # [N] dL/dz of the depth map (rasterize_backward(..., depths=...), unpacked)
 
 
 @dataclass
@@ -203,6 +205,13 @@ class RenderOutput:
     zeroed_accum: Optional[torch.Tensor] = None # [N,16] accumulator already cleared by the forward blend (one backward)
     pending: Optional[object] = None            # render(..., defer_count=True): the sort's pair count has not been read yet
     tile_order: Optional[torch.Tensor] = None   # [tiles,4] int32: the order the blend kernels' workgroups take the tiles in
+    # render(..., want_depth_map=True) (not in the reference): [H,W] sum_i z_i alpha_i T_i, background 0
+    depth_map: Optional[torch.Tensor] = None
+
+    @property
+    def alpha(self) -> torch.Tensor:
+        """The alpha (coverage) map [H,W]: 1 - final_T.  depth_map / alpha.clamp_min(eps) is the normalised depth."""
+        return 1.0 - self.final_T
 
     def wait(self) -> "RenderOutput":
         """Completes a render(..., defer_count=True): waits for the sort's pair count, trims `gaussian_indices` to it

@@ -242,9 +242,26 @@ int cugs_rasterize_forward_ordered(int width, int height, const float background
                                    float* out_final_T, int32_t* out_n_contrib, void* zero_buf, size_t zero_bytes,
                                    const uint32_t* tile_order, void* stream);
 
+/* cugs_rasterize_forward_ordered that also writes the accumulated DEPTH MAP out_depth [H,W] (not in the reference;
+ * DESIGN.md 4.13): out_depth[px] = sum_i z_i alpha_i T_i over the same contributors, in the same front-to-back order and
+ * with the same decisions as the colour channels, z_i = depths[i] of cugs_project_forward (the camera-space t.z), bit for
+ * bit; each step is fmaf(alpha_i T_i, z_i, acc) and the background does not enter.  The result equals, bit for bit, the
+ * red channel of this blend with rgb := (z, z, z) and background 0.  color, final_T and n_contrib are those of
+ * cugs_rasterize_forward_ordered, bit for bit.  The alpha (coverage) map is 1 - final_T; it needs no output.
+ * depths [n] is required whenever gaussian_indices is given; out_depth whenever the image is not empty. */
+int cugs_rasterize_forward_depth(int width, int height, const float background_host[3],
+                                 const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                 const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                 const float* opacities_act, const float* packed, float* out_color,
+                                 float* out_final_T, int32_t* out_n_contrib, void* zero_buf, size_t zero_bytes,
+                                 const uint32_t* tile_order, const float* depths, float* out_depth, void* stream);
+
 /* ---- a7: rasterize_backward (backward.cu:239-306, kernel :31-233) -------------------
  * grad_accum: [n,CUGS_GRAD_STRIDE] floats, 64-byte aligned scratch (zeroed by the callee).  A row is
- *   {dL_drgb[3], dL_dopacity_act, M1x, M1y, M2xx, M2xy, M2yy, 0...}
+ *   {dL_drgb[3], dL_dopacity_act, M1x, M1y, M2xx, M2xy, M2yy, dL_dz, 0...}
+ * Word 9, dL_dz, is the gradient of the depth map with respect to the Gaussian's camera-space depth z (= depths[i]):
+ * written by cugs_rasterize_backward_depth only, 0 otherwise.  cugs_project_backward and its fused variants add it to
+ * dL/dt.z (t = W p + t_cam), i.e. dL_dpositions += dL_dz * W[2,:], for radii > 0 - a zero word changes no bit.
  * Words 4..8 are NOT gradients: they are the MOMENTS of dL/dpower over the pixel offsets d = pixel centre - mean,
  *   M1 = sum dL/dpower * (dx, dy),   M2 = sum dL/dpower * (dx^2, dx dy, dy^2),
  * from which the reference's two tensors follow by a per-Gaussian linear map with Sigma'^-1 = (a, b, c)
@@ -284,6 +301,23 @@ int cugs_rasterize_backward_ordered(int width, int height, const float backgroun
                                     const int32_t* n_contrib, int64_t n, float* grad_accum,
                                     float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
                                     float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order, void* stream);
+
+/* cugs_rasterize_backward_ordered with the gradients of the DEPTH MAP and the ALPHA MAP (cugs_rasterize_forward_depth;
+ * not in the reference).  dL_ddepth_map [H,W] and dL_dalpha [H,W] (alpha = 1 - final_T) may each be
+ * NULL (zero).  Through the blend they add to dL_dopacity_act and to the moments (words 3..8); through z they give
+ * dL_dz in word 9 of the row.  Colour gradients (words 0..2) are those of dL_dcolor alone.  depths [n] (those of the
+ * forward) is required whenever gaussian_indices is given.  dL_ddepths [n] receives word 9 and is required exactly
+ * when the four reference-layout outputs are given (CUGS_EINVAL otherwise). */
+int cugs_rasterize_backward_depth(int width, int height, const float background_host[3],
+                                  const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                  const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                  const float* opacities_act, const float* packed,
+                                  const float* dL_dcolor, const float* final_T,
+                                  const int32_t* n_contrib, int64_t n, float* grad_accum,
+                                  float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                  float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
+                                  const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
+                                  float* dL_ddepths, void* stream);
 
 /* ---- a8+a9: project_backward (projection_backward.cu:253-344, kernel :26-247) -------
  * One launch: k_project_backward + directions + k_evaluate_sh_backward.  The incoming 2-D
