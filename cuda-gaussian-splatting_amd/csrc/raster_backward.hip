@@ -469,6 +469,7 @@ extern "C" int cugs_rasterize_backward_depth(int width, int height, const float 
 // cugsdbg_reduce9: one wave runs reduce9t on caller data.  in: [9][64] floats (value k of lane l at k*64+l,
 // k = slot); out: [64] floats (each lane's result), slots: [64] ints.
 // cugsdbg_rcp: out[i] = v_rcp_f32(in[i]).
+// cugsdbg_may_touch_quad: see k_dbg_may_touch_quad.
 namespace {
 __global__ void k_dbg_reduce9(const float* __restrict__ in, float* __restrict__ out, int* __restrict__ slots) {
     const int l = threadIdx.x;
@@ -504,6 +505,38 @@ __global__ void k_dbg_blend_exp(const float* __restrict__ q, float* __restrict__
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = cugs_blend_exp_q(q[i]);
 }
+// cugsdbg_may_touch_quad: the blends' cull against their own per-pixel decisions, one case per thread.
+// in: [n][8] floats {mean x, mean y, a, b, c, opacity, quad x, quad y} (quad x, y: the quad's integer pixel origin),
+// masks [n] (the open pixels, lane = y*8 + x; non-zero).  The record is made by write_packed (tau = ln(255 o) included)
+// and read back as the blends read it.  out: hit [n] (may_touch_quad against active_rect(mask)), pass [n] (bit l: lane l
+// is open and pixel_alpha_raw + passes_alpha_min lets the Gaussian through there), rect [n][4] (active_rect, relative
+// to the quad's first pixel centre).
+__global__ void k_dbg_may_touch_quad(int n, const float* __restrict__ in, const unsigned long long* __restrict__ masks,
+                                     int* __restrict__ hit, unsigned long long* __restrict__ pass,
+                                     float* __restrict__ rect) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* c = in + (int64_t)i * 8;
+    alignas(16) float rec[CUGS_PACKED_STRIDE];
+    write_packed(rec, 0, c[0], c[1], Sym2{c[2], c[3], c[4]}, 0.0f, 0.0f, 0.0f, c[5]);
+    const float4 r0 = reinterpret_cast<const float4*>(rec)[0], r1 = reinterpret_cast<const float4*>(rec)[1];
+    const int quad_x = (int)c[6], quad_y = (int)c[7];
+    const float qx0 = (float)quad_x + 0.5f, qy0 = (float)quad_y + 0.5f;
+    const unsigned long long active = masks[i];
+    const ActiveRect ar = active_rect(active, qx0, qy0);
+    hit[i] = may_touch_quad(r0, r1, ar.x0, ar.y0, ar.wx, ar.wy) ? 1 : 0;
+    unsigned long long p = 0ull;
+    for (int l = 0; l < 64; ++l) {
+        const float pxf = (float)(quad_x + (l & 7)) + 0.5f, pyf = (float)(quad_y + (l >> 3)) + 0.5f;
+        const float open = ((active >> l) & 1ull) ? 1.0f : 0.0f;
+        PixelEval e;
+        const float alpha = pixel_alpha_raw(pxf, pyf, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, open, e);
+        if (passes_alpha_min(alpha) != 0.0f) p |= 1ull << l;
+    }
+    pass[i] = p;
+    rect[(int64_t)i * 4 + 0] = ar.x0 - qx0; rect[(int64_t)i * 4 + 1] = ar.y0 - qy0;
+    rect[(int64_t)i * 4 + 2] = ar.wx; rect[(int64_t)i * 4 + 3] = ar.wy;
+}
 bool g_dev_backward_stats = false;
 }  // namespace
 bool cugs_dev_backward_stats() { return g_dev_backward_stats; }
@@ -530,6 +563,14 @@ extern "C" int cugsdbg_blend_exp_q(const float* q, float* out, int n, void* stre
 }
 extern "C" int cugsdbg_rcp(const float* in, float* out, int n, void* stream) {
     hipLaunchKernelGGL(k_dbg_rcp, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), in, out, n);
+    CUGS_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int cugsdbg_may_touch_quad(int n, const float* in, const unsigned long long* masks, int* hit,
+                                      unsigned long long* pass, float* rect, void* stream) {
+    if (n <= 0) return n == 0 ? 0 : CUGS_EINVAL;
+    hipLaunchKernelGGL(k_dbg_may_touch_quad, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), n, in,
+                       masks, hit, pass, rect);
     CUGS_LAUNCH_CHECK();
     return 0;
 }

@@ -550,7 +550,8 @@ static void rasterize_backward_accumulate(int img_w, int row0, int row1, const f
                                  const int32_t* tile_ranges, const int32_t* gaussian_idx,
                                  const float* means_2d, const float* cov_2d_inv, const float* rgb,
                                  const float* opacities, const float* dL_dcolor,
-                                 const float* final_T, const int32_t* n_contrib, double* acc, double* mag) {
+                                 const float* final_T, const int32_t* n_contrib, double* acc, double* mag,
+                                 double* mag_depth) {
     int ntx = (img_w + TILE - 1) / TILE;
     for (int py = row0; py < row1; ++py)
         for (int px = 0; px < img_w; ++px) {
@@ -610,6 +611,14 @@ static void rasterize_backward_accumulate(int img_w, int row0, int row1, const f
                     M[0] += fabs((double)dr0); M[1] += fabs((double)dr1); M[2] += fabs((double)dr2);
                     M[3] += clamped ? 0.0 : da_mag * exp_power;
                     M[4] += pw * ax; M[5] += pw * ay; M[6] += pw * ax * ax; M[7] += pw * ax * ay; M[8] += pw * ay * ay;
+                    if (mag_depth) {                 /* the same terms weighted by their depth j = found */
+                        double* J = mag_depth + (size_t)g * 9;
+                        const double j = (double)found;
+                        J[0] += j * fabs((double)dr0); J[1] += j * fabs((double)dr1); J[2] += j * fabs((double)dr2);
+                        J[3] += j * (clamped ? 0.0 : da_mag * exp_power);
+                        J[4] += j * pw * ax; J[5] += j * pw * ay; J[6] += j * pw * ax * ax; J[7] += j * pw * ax * ay;
+                        J[8] += j * pw * ay * ay;
+                    }
                 }
             }
         }
@@ -635,11 +644,11 @@ static void rasterize_backward_rows_impl(int img_w, int img_h, int row0, int row
                                  const float* opacities, const float* dL_dcolor,
                                  const float* final_T, const int32_t* n_contrib, int n_gaussians,
                                  float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                 float* dL_dcov_2d_inv, double* mag) {
+                                 float* dL_dcov_2d_inv, double* mag, double* mag_depth) {
     (void)img_h;
     double* acc = (double*)calloc((size_t)(n_gaussians > 0 ? n_gaussians : 1) * 9, sizeof(double));
     rasterize_backward_accumulate(img_w, row0, row1, bg, tile_ranges, gaussian_idx, means_2d, cov_2d_inv, rgb, opacities,
-                                  dL_dcolor, final_T, n_contrib, acc, mag);
+                                  dL_dcolor, final_T, n_contrib, acc, mag, mag_depth);
     rasterize_backward_finish(n_gaussians, acc, dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv);
     free(acc);
 }
@@ -649,13 +658,13 @@ static void rasterize_backward_rows_impl(int img_w, int img_h, int row0, int row
  * the bands' tables are added to the total in band order (`omp ordered`) - so the result is the same for every
  * thread count, and differs from the one-table serial sum only by fp64 association (~1e-16 relative, before the one
  * rounding to fp32).  Memory: (nthreads + 1) tables of 72 bytes per Gaussian.  Returns 0, or -1 if out of memory. */
-int orc_rasterize_backward_rows_mt(int nthreads, int img_w, int img_h, int row0, int row1, const float bg[3],
+static int rasterize_backward_rows_mt_impl(int nthreads, int img_w, int img_h, int row0, int row1, const float bg[3],
                                    const int32_t* tile_ranges, const int32_t* gaussian_idx,
                                    const float* means_2d, const float* cov_2d_inv, const float* rgb,
                                    const float* opacities, const float* dL_dcolor,
                                    const float* final_T, const int32_t* n_contrib, int n_gaussians,
                                    float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                   float* dL_dcov_2d_inv, double* mag /* optional [n,9], zeroed by the caller */) {
+                                   float* dL_dcov_2d_inv, double* mag, double* mag_depth) {
     (void)img_h;
     const int BAND = 64;
     const size_t cells = (size_t)(n_gaussians > 0 ? n_gaussians : 1) * 9;
@@ -669,7 +678,8 @@ int orc_rasterize_backward_rows_mt(int nthreads, int img_w, int img_h, int row0,
     {
         double* acc = (double*)calloc(cells, sizeof(double));
         double* tmag = mag ? (double*)calloc(cells, sizeof(double)) : NULL;
-        if (!acc || (mag && !tmag)) {
+        double* tdep = mag_depth ? (double*)calloc(cells, sizeof(double)) : NULL;
+        if (!acc || (mag && !tmag) || (mag_depth && !tdep)) {
 #pragma omp atomic write
             failed = 1;
             free(acc);
@@ -680,20 +690,49 @@ int orc_rasterize_backward_rows_mt(int nthreads, int img_w, int img_h, int row0,
             const int r0 = row0 + b * BAND, r1 = (r0 + BAND < row1) ? r0 + BAND : row1;
             if (acc)
                 rasterize_backward_accumulate(img_w, r0, r1, bg, tile_ranges, gaussian_idx, means_2d, cov_2d_inv, rgb,
-                                              opacities, dL_dcolor, final_T, n_contrib, acc, tmag);
+                                              opacities, dL_dcolor, final_T, n_contrib, acc, tmag, tdep);
 #pragma omp ordered
             if (acc)
                 for (size_t i = 0; i < cells; ++i) {
                     if (acc[i] != 0.0) { total[i] += acc[i]; acc[i] = 0.0; }
                     if (tmag && tmag[i] != 0.0) { mag[i] += tmag[i]; tmag[i] = 0.0; }
+                    if (tdep && tdep[i] != 0.0) { mag_depth[i] += tdep[i]; tdep[i] = 0.0; }
                 }
         }
         free(acc);
         free(tmag);
+        free(tdep);
     }
     if (!failed) rasterize_backward_finish(n_gaussians, total, dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv);
     free(total);
     return failed ? -1 : 0;
+}
+
+int orc_rasterize_backward_rows_mt(int nthreads, int img_w, int img_h, int row0, int row1, const float bg[3],
+                                   const int32_t* tile_ranges, const int32_t* gaussian_idx,
+                                   const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                   const float* opacities, const float* dL_dcolor,
+                                   const float* final_T, const int32_t* n_contrib, int n_gaussians,
+                                   float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                   float* dL_dcov_2d_inv, double* mag /* optional [n,9], zeroed by the caller */) {
+    return rasterize_backward_rows_mt_impl(nthreads, img_w, img_h, row0, row1, bg, tile_ranges, gaussian_idx, means_2d,
+                                           cov_2d_inv, rgb, opacities, dL_dcolor, final_T, n_contrib, n_gaussians,
+                                           dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, mag, NULL);
+}
+
+/* ... plus mag_depth ([n,9] doubles, zeroed by the caller): the nine magnitude sums with every term weighted by its
+ * DEPTH j in its pixel's back-to-front replay (T has been divided j times, S summed over j - 1 terms) - the
+ * recurrences' rounding grows with j (oracle/parity.py: blend_bound_report). */
+int orc_rasterize_backward_rows_mt_depth(int nthreads, int img_w, int img_h, int row0, int row1, const float bg[3],
+                                         const int32_t* tile_ranges, const int32_t* gaussian_idx,
+                                         const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                         const float* opacities, const float* dL_dcolor,
+                                         const float* final_T, const int32_t* n_contrib, int n_gaussians,
+                                         float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                         float* dL_dcov_2d_inv, double* mag, double* mag_depth) {
+    return rasterize_backward_rows_mt_impl(nthreads, img_w, img_h, row0, row1, bg, tile_ranges, gaussian_idx, means_2d,
+                                           cov_2d_inv, rgb, opacities, dL_dcolor, final_T, n_contrib, n_gaussians,
+                                           dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, mag, mag_depth);
 }
 
 void orc_rasterize_backward_rows(int img_w, int img_h, int row0, int row1, const float bg[3],
@@ -705,7 +744,7 @@ void orc_rasterize_backward_rows(int img_w, int img_h, int row0, int row1, const
                                  float* dL_dcov_2d_inv) {
     rasterize_backward_rows_impl(img_w, img_h, row0, row1, bg, tile_ranges, gaussian_idx, means_2d, cov_2d_inv, rgb,
                                  opacities, dL_dcolor, final_T, n_contrib, n_gaussians, dL_drgb, dL_dopacity_act,
-                                 dL_dmeans_2d, dL_dcov_2d_inv, NULL);
+                                 dL_dmeans_2d, dL_dcov_2d_inv, NULL, NULL);
 }
 
 /* the same sums plus their magnitudes (see rasterize_backward_rows_impl) */
@@ -717,7 +756,20 @@ void orc_rasterize_backward_magnitudes(int img_w, int img_h, const float bg[3], 
                                        float* dL_dcov_2d_inv, double* mag) {
     rasterize_backward_rows_impl(img_w, img_h, 0, img_h, bg, tile_ranges, gaussian_idx, means_2d, cov_2d_inv, rgb,
                                  opacities, dL_dcolor, final_T, n_contrib, n_gaussians, dL_drgb, dL_dopacity_act,
-                                 dL_dmeans_2d, dL_dcov_2d_inv, mag);
+                                 dL_dmeans_2d, dL_dcov_2d_inv, mag, NULL);
+}
+
+/* ... plus the depth-weighted magnitudes (see orc_rasterize_backward_rows_mt_depth) */
+void orc_rasterize_backward_magnitudes_depth(int img_w, int img_h, const float bg[3], const int32_t* tile_ranges,
+                                             const int32_t* gaussian_idx, const float* means_2d,
+                                             const float* cov_2d_inv, const float* rgb, const float* opacities,
+                                             const float* dL_dcolor, const float* final_T, const int32_t* n_contrib,
+                                             int n_gaussians, float* dL_drgb, float* dL_dopacity_act,
+                                             float* dL_dmeans_2d, float* dL_dcov_2d_inv, double* mag,
+                                             double* mag_depth) {
+    rasterize_backward_rows_impl(img_w, img_h, 0, img_h, bg, tile_ranges, gaussian_idx, means_2d, cov_2d_inv, rgb,
+                                 opacities, dL_dcolor, final_T, n_contrib, n_gaussians, dL_drgb, dL_dopacity_act,
+                                 dL_dmeans_2d, dL_dcov_2d_inv, mag, mag_depth);
 }
 
 void orc_rasterize_backward(int img_w, int img_h, const float bg[3], const int32_t* tile_ranges,

@@ -23,6 +23,7 @@ _lib.orc_expf.restype = C.c_float
 _lib.orc_expf.argtypes = [C.c_float]
 _lib.orc_project_sh_forward_mt.restype = C.c_int
 _lib.orc_rasterize_backward_rows_mt.restype = C.c_int
+_lib.orc_rasterize_backward_rows_mt_depth.restype = C.c_int
 
 TILE = 16
 
@@ -181,12 +182,15 @@ def rasterize_backward(w, h, bg, tile_ranges, gidx, means_2d, cov_2d_inv, rgb, o
 
 
 def rasterize_backward_magnitudes(w, h, bg, tile_ranges, gidx, means_2d, cov_2d_inv, rgb, opacities, dL_dcolor,
-                                  final_T, n_contrib, n, rows=None, threads=1):
+                                  final_T, n_contrib, n, rows=None, threads=1, depth_weighted=False):
     """rasterize_backward plus `mag` [n, 9] (float64): the sums of the MAGNITUDES of the terms of each accumulated
     gradient - sum |drgb_c| (3), sum |dL_dopa|, sum |dpw dx|, sum |dpw dy|, sum |dpw| dx^2, sum |dpw dx dy|,
     sum |dpw| dy^2 - which bound the rounding error of any fp32 evaluation and summation of those terms.  dL_dopa
     and dpw = dL_dpower enter with the magnitude of the OPERANDS of dL_dalpha (a difference per channel and over the
-    channels), not of its value."""
+    channels), not of its value.
+    `depth_weighted`: also `mag_depth` [n, 9] (float64), the same nine sums with each term weighted by its depth j in
+    its pixel's back-to-front replay (T divided j times, S summed over j - 1 terms): the rounding of those recurrences
+    grows with j (oracle/parity.py: blend_bound_report)."""
     bg_a = _f(bg)
     tr, gi = _i(tile_ranges), _i(gidx)
     m, c, r, o = _f(means_2d), _f(cov_2d_inv), _f(rgb), _f(opacities)
@@ -194,20 +198,23 @@ def rasterize_backward_magnitudes(w, h, bg, tile_ranges, gidx, means_2d, cov_2d_
     out = dict(dL_drgb=np.empty((n, 3), np.float32), dL_dopacity_act=np.empty(n, np.float32),
                dL_dmeans_2d=np.empty((n, 2), np.float32), dL_dcov_2d_inv=np.empty((n, 3), np.float32),
                mag=np.zeros((n, 9), np.float64))
+    dep = ()
+    if depth_weighted:
+        out["mag_depth"] = np.zeros((n, 9), np.float64)
+        dep = (_p(out["mag_depth"]),)
     if threads > 1 or rows is not None:
         r0, r1 = (0, h) if rows is None else rows
-        rc = _lib.orc_rasterize_backward_rows_mt(C.c_int(max(1, threads)), C.c_int(w), C.c_int(h), C.c_int(r0),
-                                                 C.c_int(r1), _p(bg_a), _p(tr), _p(gi), _p(m), _p(c), _p(r), _p(o),
-                                                 _p(g), _p(ft), _p(nc), C.c_int(n), _p(out["dL_drgb"]),
-                                                 _p(out["dL_dopacity_act"]), _p(out["dL_dmeans_2d"]),
-                                                 _p(out["dL_dcov_2d_inv"]), _p(out["mag"]))
+        entry = _lib.orc_rasterize_backward_rows_mt_depth if depth_weighted else _lib.orc_rasterize_backward_rows_mt
+        rc = entry(C.c_int(max(1, threads)), C.c_int(w), C.c_int(h), C.c_int(r0), C.c_int(r1), _p(bg_a), _p(tr), _p(gi),
+                   _p(m), _p(c), _p(r), _p(o), _p(g), _p(ft), _p(nc), C.c_int(n), _p(out["dL_drgb"]),
+                   _p(out["dL_dopacity_act"]), _p(out["dL_dmeans_2d"]), _p(out["dL_dcov_2d_inv"]), _p(out["mag"]), *dep)
         if rc != 0:
             raise MemoryError("oracle backward: per-thread accumulator tables do not fit")
         return out
-    _lib.orc_rasterize_backward_magnitudes(C.c_int(w), C.c_int(h), _p(bg_a), _p(tr), _p(gi), _p(m), _p(c), _p(r), _p(o),
-                                           _p(g), _p(ft), _p(nc), C.c_int(n), _p(out["dL_drgb"]),
-                                           _p(out["dL_dopacity_act"]), _p(out["dL_dmeans_2d"]),
-                                           _p(out["dL_dcov_2d_inv"]), _p(out["mag"]))
+    entry = _lib.orc_rasterize_backward_magnitudes_depth if depth_weighted else _lib.orc_rasterize_backward_magnitudes
+    entry(C.c_int(w), C.c_int(h), _p(bg_a), _p(tr), _p(gi), _p(m), _p(c), _p(r), _p(o), _p(g), _p(ft), _p(nc), C.c_int(n),
+          _p(out["dL_drgb"]), _p(out["dL_dopacity_act"]), _p(out["dL_dmeans_2d"]), _p(out["dL_dcov_2d_inv"]),
+          _p(out["mag"]), *dep)
     return out
 
 

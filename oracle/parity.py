@@ -114,6 +114,89 @@ def blend_accumulator_report(got: dict, want: dict, mag, cov_2d_inv, list_entrie
     return out
 
 
+def blend_bound_report(got: dict, want: dict, mags: dict, cov_2d_inv, list_entries) -> dict:
+    """EVERY element of the blend backward's accumulators against the fp32 bound of its own terms - the all-element
+    form of the rule `blend_accumulator_report` applies only to elements already over the bar:
+
+      |g - r| <= B * m + R * m_depth  with B = (32 + 4 entries) * 2^-24 (the same B, per Gaussian), and
+      g == 0.0 exactly wherever m == 0 (no term at all: a sum delivered to the wrong row shows up here).
+
+    R * m_depth is the one thing B does not cover: every term carries the T and S (D) recurrences of its pixel's
+    back-to-front replay, and a term at depth j (T divided j times) inherits j steps of their rounding.  The kernel
+    forms T *= v_rcp_f32(1 - alpha) (rcp <= 1 ulp, product 0.5 ulp), the oracle T /= (1 - alpha) (0.5 ulp): at most
+    2 ulp apart per step; D and the oracle's S add one rounding each per step, within the operand magnitudes that
+    dL/dalpha's terms already count: 1 ulp.  So R = 3 * 2^-24 and m_depth = sum j |term| (the oracle's `mag_depth`,
+    rasterize_backward_magnitudes(..., depth_weighted=True); without it the depth term is 0, a stricter bound).
+    Measured, the kernel's T drifts from the oracle's by ~0.15 ulp per step on average (a biased reciprocal): 77 ulp
+    at depth ~500, past B alone.
+
+    got / want: the four reference-layout tensors (ACCUMULATORS), optionally also "dL_ddepths" [n] (word 9 of the
+    row on the depth-map route); want holds the oracle's fp64 sums (rounded to fp32 per channel - half an ulp of each
+    channel's sum, far inside 32 ulp of its magnitudes).  cov_2d_inv [n, 3]; list_entries [n] as above.
+    mags: {channel: the dict orc.rasterize_backward_magnitudes(..., depth_weighted=True) returns ("mag", "mag_depth")},
+    "colour" always, "depth" / "alpha" on the depth-map route.  The depth-map kernel forms ONE per-step dot product G = sum_c dL/dC_c c_c + dL/dD z and one
+    running D whose start carries the alpha map (D -= final_T dL/dA), so every opacity and geometry term it sums is the
+    sum of the corresponding terms of three channel blends with the same decisions:
+      colour  the usual call;
+      depth   rgb := z, background 0, dL_dcolor := (dL/dD, 0, 0) - its mag[:, 0] also bounds dL_ddepths;
+      alpha   rgb := 0, background (-1, 0, 0), dL_dcolor := (dL/dA, 0, 0) - the kernel's own formulation (the
+              identity sum alpha T + final_T = 1 makes it the channel c = 1, bg = 0).
+    The magnitudes count the OPERANDS of each term, so by the triangle inequality the combined term's magnitude is at
+    most the sum of the three, and the sum of the three channels' m bounds the combined sum's rounding with the same
+    B.  dL_drgb takes the colour channel's bound alone (the depth and alpha channels reach no colour).
+    Returns {tensor: {"worst_diff_over_bound", "worst": {...}, "beyond_bound", "nonzero_without_terms",
+    "elements", "ok"}} - the worst ratio per tensor whether it passes or not."""
+    n = np.asarray(mags["colour"]["mag"]).shape[0]
+    entries = np.asarray(list_entries, np.float64).reshape(n)
+    B = ((32.0 + 4.0 * entries) * 2.0 ** -24)[:, None]
+    R = 3.0 * 2.0 ** -24
+
+    def eff(ch):                                             # B * eff = B m + R m_depth, per column
+        m = np.asarray(ch["mag"], np.float64)
+        return m + (R / B) * np.asarray(ch["mag_depth"], np.float64) if "mag_depth" in ch else m
+    per = {k: eff(v) for k, v in mags.items()}
+    total = sum(per.values())
+    a, b, c = (np.abs(np.asarray(cov_2d_inv, np.float64)[:, i]) for i in range(3))
+    bound = {
+        "dL_drgb": per["colour"][:, 0:3],
+        "dL_dopacity_act": total[:, 3:4],
+        "dL_dmeans_2d": np.stack([a * total[:, 4] + b * total[:, 5], b * total[:, 4] + c * total[:, 5]], axis=1),
+        "dL_dcov_2d_inv": np.stack([0.5 * total[:, 6], total[:, 7], 0.5 * total[:, 8]], axis=1),
+    }
+    if "dL_ddepths" in got:
+        bound["dL_ddepths"] = per["depth"][:, 0:1]
+    out = {}
+    for name, m in bound.items():
+        g = np.asarray(got[name], np.float64).reshape(m.shape)
+        r = np.asarray(want[name], np.float64).reshape(m.shape)
+        diff = np.abs(g - r)
+        allowed = B * m + 1e-37                     # 1e-37: below the fp32 normal range only (denormal results)
+        zero_terms = m == 0.0
+        ratio = np.where(zero_terms, np.where(g == 0.0, 0.0, np.inf), diff / allowed)
+        ratio = np.where(np.isnan(g), np.inf, ratio)
+        j = np.unravel_index(int(np.argmax(ratio)), m.shape)
+        beyond = int(np.count_nonzero(ratio > 1.0))
+        stray = int(np.count_nonzero(zero_terms & (g != 0.0)))
+        out[name] = {"worst_diff_over_bound": float(ratio[j]), "beyond_bound": beyond, "nonzero_without_terms": stray,
+                     "elements": int(m.size), "ok": beyond == 0,
+                     "worst": {"gaussian": int(j[0]), "component": int(j[1]), "got": float(g[j]), "want": float(r[j]),
+                               "sum_of_term_magnitudes": float(m[j]), "entries": int(entries[j[0]])}}
+    return out
+
+
+def format_bound_report(rep: dict, title: str = "") -> str:
+    """One line per tensor of a `blend_bound_report`: the worst diff/bound and where it sits."""
+    lines = [title] if title else []
+    for name, v in rep.items():
+        w = v["worst"]
+        lines.append("  %-16s worst diff/bound %.3g (Gaussian %d component %d: got %.6e want %.6e sum|terms| %.3e, "
+                     "%d entries); %d of %d beyond the bound, %d non-zero without terms" % (
+                         name, v["worst_diff_over_bound"], w["gaussian"], w["component"], w["got"], w["want"],
+                         w["sum_of_term_magnitudes"], w["entries"], v["beyond_bound"], v["elements"],
+                         v["nonzero_without_terms"]))
+    return "\n".join(lines)
+
+
 def format_report(rep: dict, title: str = "") -> str:
     """Human-readable table (printed by tests with -s, by smoke() and by tools)."""
     lines = [title] if title else []

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import GRAD_NAMES, blend_stage_report, load_parity, max_err_over_max, np_, oracle_forward
+from util import GRAD_NAMES, blend_stage_check, load_parity, max_err_over_max, np_, oracle_forward
 
 pytestmark = pytest.mark.gpu
 
@@ -89,7 +89,11 @@ def test_fullsize_frame_matches_oracle(pkg, orc, dev, full):
     for name, v in rep["per_tensor"].items():
         assert v["over_scale"] <= 1e-4, (name, v)
     out2 = pkg.render(model, cam, settings)                            # a fresh accumulator for the stage-level pass
-    stage = blend_stage_report(pkg, orc, dev, out2, ref, g, (0.0, 0.0, 0.0), wl.n, wl.width, wl.height, threads=th)
+    # the launch render_backward makes: render()'s tile order (>= 2 M pairs) and the accumulator its forward cleared
+    assert out2.tile_order is not None
+    stage = blend_stage_check(pkg, orc, dev, out2, ref, g, (0.0, 0.0, 0.0), wl.n, wl.width, wl.height, threads=th,
+                              tile_order=out2.tile_order, zeroed_accum=out2.zeroed_accum, label="config 3 full frame")
+    out2.zeroed_accum = None                                           # consumed: render_backward below fills its own
     print(par.format_report(stage, "config 3, full frame: blend-backward accumulators with the magnitude of their terms"))
     for name, v in stage.items():
         assert v["over_scale"] <= 1e-4, (name, v)

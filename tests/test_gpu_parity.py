@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 import torch
 
-from util import blend_stage_report, load_parity, max_err_over_max, max_rel_err, np_, oracle_backward, oracle_forward
+from util import (blend_stage_check, check_blend_bounds, load_parity, max_err_over_max, max_rel_err, np_, oracle_backward,
+                  oracle_blend_terms, oracle_forward)
 
 pytestmark = pytest.mark.gpu
 
@@ -385,7 +386,9 @@ def test_render_backward_parity(pkg, orc, dev, n, w, h, deg, mu_s, bg, view):
         assert max_rel_err(got, refb[name], floor_frac=1e-3) <= 20 * GRAD_TOL, name   # element-wise, floor 1e-3 of scale
     # SURVEY 8d's own metric (floor 1e-6 of the scale) is printed above; where it exceeds 1e-4 the element must be a
     # cancelling sum: |diff| within the fp32 bound of the magnitudes of its own terms, shown per accumulator
-    stage = blend_stage_report(pkg, orc, dev, out, ref, g, bg, n, w, h)
+    # ... and EVERY accumulator element within the fp32 bound of its own terms (exactly zero where it has none)
+    stage = blend_stage_check(pkg, orc, dev, out, ref, g, bg, n, w, h, tile_order=out.tile_order,
+                              label=f"render_backward_parity {w}x{h}")
     print(par.format_report(stage, "blend-backward accumulators, element-wise with the magnitude of their terms:"))
     for name, v in stage.items():
         assert v["over_scale"] <= GRAD_TOL, (name, v)
@@ -443,8 +446,64 @@ def test_blend_with_rows_beyond_32bit_byte_offsets(pkg, orc, dev):
         got = getattr(rb, name)
         assert max_err_over_max(np_(got[base:]), want[name]) <= GRAD_TOL, name
         assert not bool(got[:base].any()), name                  # nothing landed in a truncated address
+    # every element within the fp32 bound of its own terms
+    terms, mags = oracle_blend_terms(orc, ref, g, bg, n, w, h)
+    check_blend_bounds({k: np_(getattr(rb, k)[base:]) for k in terms}, terms, mags, ref["cov_2d_inv"],
+                       np.bincount(ref["values"], minlength=n), "rows beyond 2^26 (WIDE, unpacked, colour)")
     del means, cov, rgb, opa, rb
     torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_depth_blend_with_rows_beyond_32bit_byte_offsets(pkg, orc, dev, packed):
+    """k_raster_backward<PACKED, WIDE = true, DEPTH = true>: the depth-map backward on an accumulator larger than 4 GiB.
+    The small scene sits at rows 2^26 + 5 .. of otherwise empty tables: the unpacked route takes the oracle's four
+    arrays and depths there, the packed route the projection's own packed records (render() of the small scene)
+    placed there.  Every element of the four accumulators and of dL_ddepths within the fp32 bound of its terms (colour
+    + depth + alpha channels), nothing in the rows below, each >4 GiB accumulator freed before the next."""
+    w, h, n = 160, 120, 3000
+    base = (1 << 26) + 5
+    big = base + n
+    arrays, cam = _scene(pkg, n, w, h, 0, seed=6, mu_s=-3.3)
+    bg = (0.2, 0.1, 0.0)
+    ref = oracle_forward(orc, arrays, cam, degree=0, bg=bg)
+    g = pkg.scene.make_dl_dcolor(w, h)
+    rng = np.random.default_rng(61)
+    dD = (rng.standard_normal((h, w)) * 1e-3).astype(np.float32)
+    dA = (rng.standard_normal((h, w)) * 1e-3).astype(np.float32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def table(a):
+        a = torch.as_tensor(a).to(dev)
+        full = torch.zeros((big,) + tuple(a.shape[1:]), dtype=torch.float32, device=dev)
+        full[base:] = a
+        return full
+    means, cov, rgb, opa, depths = (table(ref[k]) for k in ("means_2d", "cov_2d_inv", "rgb", "opacities_act", "depths"))
+    pk = None
+    if packed:
+        small = pkg.render(pkg.scene.to_model(arrays, dev), cam, pkg.RenderSettings(background=list(bg), active_sh_degree=0),
+                           for_backward=True)
+        assert np.array_equal(np_(small.gaussian_indices), ref["values"])
+        pk = table(small.packed)
+        del small
+    idx = t(ref["values"]) + base
+    ranges = t(ref["tile_ranges"])
+    fwd = pkg.rasterize_forward(means, cov, rgb, opa, ranges, idx, w, h, bg, packed=pk, depths=depths)
+    assert np.array_equal(np_(fwd.color).view(np.uint32), ref["color"].view(np.uint32))
+    assert np.array_equal(np_(fwd.n_contrib), ref["n_contrib"])
+    rb = pkg.rasterize_backward(t(g), means, cov, rgb, opa, ranges, idx, fwd.final_T, fwd.n_contrib, w, h, bg, big,
+                                packed=pk, depths=depths, dL_ddepth_map=t(dD), dL_dalpha=t(dA))
+    names = ("dL_drgb", "dL_dopacity_act", "dL_dmeans_2d", "dL_dcov_2d_inv", "dL_ddepths")
+    for name in names:
+        assert not bool(getattr(rb, name)[:base].any()), name   # nothing landed in a truncated address
+    assert not bool(rb.grad_accum[:base].any())
+    got = {k: np_(getattr(rb, k)[base:]) for k in names}
+    del means, cov, rgb, opa, depths, pk, rb, fwd
+    torch.cuda.empty_cache()
+    terms, mags = oracle_blend_terms(orc, ref, g, bg, n, w, h, dD=dD, dA=dA, depth_route=True)
+    assert float(np.abs(terms["dL_ddepths"]).max()) > 0.0
+    check_blend_bounds(got, terms, mags, ref["cov_2d_inv"], np.bincount(ref["values"], minlength=n),
+                       f"rows beyond 2^26 (WIDE, DEPTH, {'packed' if packed else 'unpacked'})")
 
 
 def test_render_with_more_than_2_26_gaussians(pkg, dev):

@@ -80,3 +80,67 @@ def blend_stage_report(pkg, orc, dev, out, ref, g, bg, n, w, h, rows=None, threa
     got = {k: np_(getattr(rb, k)) for k in par.ACCUMULATORS}
     entries = np.bincount(ref["values"], minlength=n)
     return par.blend_accumulator_report(got, want, want["mag"], ref["cov_2d_inv"], entries)
+
+
+def oracle_blend_terms(orc, ref, g, bg, n, w, h, dD=None, dA=None, depth_route=False, rows=None, threads=1):
+    """The oracle's fp64 sums and term magnitudes for one blend backward, per channel (oracle/parity.py:
+    blend_bound_report explains the three channels): returns (want, mags).  `depth_route`: the depth-map kernel
+    (dL/dD and dL/dA, either None = zero), whose word 9 is compared as want["dL_ddepths"]."""
+    par = load_parity()
+    geo = (ref["tile_ranges"], ref["values"], ref["means_2d"], ref["cov_2d_inv"])
+    tail = (ref["final_T"], ref["n_contrib"], n)
+
+    def run(rgb, bg_, dcolor):
+        return orc.rasterize_backward_magnitudes(w, h, bg_, *geo, np.ascontiguousarray(rgb, np.float32),
+                                                 ref["opacities_act"], np.ascontiguousarray(dcolor, np.float32), *tail,
+                                                 rows=rows, threads=threads, depth_weighted=True)
+
+    def red(m):
+        d = np.zeros((h, w, 3), np.float32)
+        if m is not None:
+            d[..., 0] = m
+        return d
+
+    col = run(ref["rgb"], bg, g)
+    want = {k: col[k].astype(np.float64) for k in par.ACCUMULATORS}
+    mags = {"colour": col}
+    if depth_route:
+        zr = np.zeros((n, 3), np.float32)
+        zr[:, 0] = ref["depths"]
+        dep = run(zr, (0.0, 0.0, 0.0), red(dD))
+        alp = run(np.zeros((n, 3), np.float32), (-1.0, 0.0, 0.0), red(dA))
+        for k in par.ACCUMULATORS[1:]:
+            want[k] = want[k] + dep[k] + alp[k]
+        want["dL_ddepths"] = dep["dL_drgb"][:, 0].astype(np.float64)
+        mags["depth"], mags["alpha"] = dep, alp
+    return want, mags
+
+
+def check_blend_bounds(got, want, mags, cov_2d_inv, list_entries, label=""):
+    """oracle/parity.py blend_bound_report on every element; prints the worst diff/bound per tensor (also when it
+    passes) and fails with the same table."""
+    par = load_parity()
+    rep = par.blend_bound_report(got, want, mags, cov_2d_inv, list_entries)
+    table = par.format_bound_report(rep, "all-element fp32 term bound: " + label)
+    print(table)
+    assert all(v["ok"] for v in rep.values()), table
+    return rep
+
+
+def blend_stage_check(pkg, orc, dev, out, ref, g, bg, n, w, h, rows=None, threads=1, tile_order=None,
+                      zeroed_accum=None, label=""):
+    """blend_stage_report's stage run (with the launch's tile order and accumulator when given) checked both ways:
+    returns the over-the-bar report of blend_accumulator_report and asserts check_blend_bounds on every element."""
+    import torch
+    par = load_parity()
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    rb = pkg.rasterize_backward(t(g), out.means_2d, out.cov_2d_inv, out.rgb, out.opacities_act, out.tile_ranges,
+                                out.gaussian_indices, out.final_T, out.n_contrib, w, h, bg, n, packed=out.packed,
+                                tile_order=tile_order, zeroed_accum=zeroed_accum)
+    want, mags = oracle_blend_terms(orc, ref, g, bg, n, w, h, rows=rows, threads=threads)
+    got = {k: np_(getattr(rb, k)) for k in par.ACCUMULATORS}
+    entries = np.bincount(ref["values"], minlength=n)
+    old = par.blend_accumulator_report(got, {k: v.astype(np.float32) for k, v in want.items()}, mags["colour"]["mag"],
+                                       ref["cov_2d_inv"], entries)
+    check_blend_bounds(got, want, mags, ref["cov_2d_inv"], entries, label)
+    return old
