@@ -54,6 +54,12 @@ class McmcFused(C.Structure):
 
 MCMC_STREAM_NOISE, MCMC_STREAM_JITTER, MCMC_STREAM_SAMPLE = 0, 1, 2     # CUGS_MCMC_STREAM_*
 
+
+class PoseGrad(C.Structure):
+    """struct cugs_pose_grad."""
+    _fields_ = [("dL_dview", C.c_void_p), ("rows", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -129,6 +135,14 @@ SIGNATURES = {
                                 C.c_size_t, _P, _P, _P]),
     "cugs_project_backward_adam_mcmc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
                                              C.POINTER(AdamFused), C.POINTER(McmcFused), _P, _P]),
+    "cugs_pose_grad_workspace_bytes": (C.c_size_t, [_L]),
+    "cugs_project_backward_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F,
+                                        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(PoseGrad), _P]),
+    "cugs_project_backward_adam_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
+                                             C.POINTER(AdamFused), _P, C.POINTER(PoseGrad), _P]),
+    "cugs_project_backward_adam_mcmc_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
+                                                  C.POINTER(AdamFused), C.POINTER(McmcFused), _P, C.POINTER(PoseGrad),
+                                                  _P]),
     "cugs_ply_vertex_floats": (_I, [_I, _I]),
     "cugs_ply_pack": (_I, [_L, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     "cugs_ply_unpack": (_I, [_L, _I, _I, _P, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),

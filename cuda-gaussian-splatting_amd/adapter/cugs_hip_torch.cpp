@@ -318,7 +318,8 @@ ProjectionBackwardOutput project_backward_impl(const torch::Tensor* accum, const
                                                const torch::Tensor& positions, const torch::Tensor& rotations,
                                                const torch::Tensor& scales, const torch::Tensor& opacities,
                                                const torch::Tensor& sh_coeffs, const torch::Tensor& radii,
-                                               const cugs_camera& camera, int degree, float scale_modifier) {
+                                               const cugs_camera& camera, int degree, float scale_modifier,
+                                               const cugs_pose_grad* pose = nullptr) {
     TORCH_CHECK(positions.is_cuda(), "positions must be on CUDA");
     const int64_t n = positions.size(0);
     ProjectionBackwardOutput o;
@@ -332,6 +333,19 @@ ProjectionBackwardOutput project_backward_impl(const torch::Tensor* accum, const
     auto pos = f32c(positions), rot = f32c(rotations), scl = f32c(scales), opa = f32c(opacities), rad = radii.contiguous();
     auto cm = gm.defined() ? gm.contiguous() : gm, cc = gc.defined() ? gc.contiguous() : gc;
     auto cr = gr.defined() ? gr.contiguous() : gr, co = go.defined() ? go.contiguous() : go;
+    if (pose) {
+        check(cugs_project_backward_pose(n, static_cast<int>(sh.size(2)), degree, ptr<float>(pos), ptr<float>(rot),
+                                         ptr<float>(scl), ptr<float>(opa), ptr<float>(sh), ptr<int32_t>(rad),
+                                         colour_gate ? ptr<uint8_t>(*colour_gate) : nullptr, &camera, scale_modifier,
+                                         accum ? ptr<float>(*accum) : nullptr, ptr<float>(cm), ptr<float>(cc),
+                                         ptr<float>(cr), ptr<float>(co), ptr<float>(o.dL_dpositions),
+                                         ptr<float>(o.dL_drotations), ptr<float>(o.dL_dscales),
+                                         ptr<float>(o.dL_dopacities), ptr<float>(o.dL_dsh_coeffs),
+                                         d_means_out ? ptr<float>(*d_means_out) : nullptr,
+                                         /*dL_drgb_gated_out=*/nullptr, pose, stream_of(positions)),
+              "cugs_project_backward_pose");
+        return o;
+    }
     check(cugs_project_backward(n, static_cast<int>(sh.size(2)), degree, ptr<float>(pos), ptr<float>(rot), ptr<float>(scl),
                                 ptr<float>(opa), ptr<float>(sh), ptr<int32_t>(rad),
                                 colour_gate ? ptr<uint8_t>(*colour_gate) : nullptr, &camera, scale_modifier,
@@ -514,7 +528,7 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& ro, const ModelTensors& model,
                                const cugs_camera& camera, const RenderSettings& settings, FusedAdam* fused,
                                const MCMCController* mcmc, int step, const torch::Tensor& dL_ddepth_map,
-                               const torch::Tensor& dL_dalpha) {
+                               const torch::Tensor& dL_dalpha, bool want_camera_grad) {
     TORCH_CHECK(!mcmc || fused, "the fused MCMC route needs the FusedAdam (otherwise: compute_regularization, step, "
                 "inject_noise)");
     TORCH_CHECK(dL_dcolor.is_cuda(), "dL_dcolor must be on CUDA device");                             // rasterizer.cpp:122-124
@@ -528,6 +542,7 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
         o.dL_dpositions = torch::zeros({0, 3}, fopt(dL_dcolor)); o.dL_drotations = torch::zeros({0, 4}, fopt(dL_dcolor));
         o.dL_dscales = torch::zeros({0, 3}, fopt(dL_dcolor)); o.dL_dopacities = torch::zeros({0, 1}, fopt(dL_dcolor));
         o.dL_dsh_coeffs = torch::zeros_like(model.sh_coeffs); o.dL_dmeans_2d = torch::zeros({0, 2}, fopt(dL_dcolor));
+        if (want_camera_grad) o.dL_dviewmat = torch::zeros({4, 4}, fopt(dL_dcolor));
         return o;
     }
     const int degree = std::min(settings.active_sh_degree, max_sh_degree(model.sh_coeffs));
@@ -551,6 +566,15 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                                  settings.background, static_cast<int>(n), packed, /*unpack=*/false, zeroed, ro.tile_order,
                                  depth_grads ? ro.depths : torch::Tensor(), dL_ddepth_map, dL_dalpha);
     o.dL_dmeans_2d = torch::empty({n, 2}, fopt(dL_dcolor));
+    // the camera gradient: its output and the reduction's workspace, both stream-ordered allocations
+    cugs_pose_grad pose{};
+    torch::Tensor pose_ws;
+    if (want_camera_grad) {
+        o.dL_dviewmat = torch::empty({4, 4}, fopt(dL_dcolor));
+        const size_t bytes = cugs_pose_grad_workspace_bytes(n);
+        pose_ws = torch::empty({static_cast<int64_t>(bytes)}, dL_dcolor.options().dtype(torch::kUInt8));
+        pose = cugs_pose_grad{ptr<float>(o.dL_dviewmat), nullptr, pose_ws.data_ptr(), bytes};
+    }
     if (fused) {                                                // a8 + a9 + a11 in one launch, parameters updated in place
         const auto& pr = fused->params();
         TORCH_CHECK(pr[0].data_ptr() == model.positions.data_ptr() && pr[1].data_ptr() == model.sh_coeffs.data_ptr(),
@@ -561,6 +585,17 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
         auto radii = ro.radii.contiguous(), gate = ro.colour_gate.contiguous();
         if (mcmc) {
             const cugs_mcmc_fused mc = mcmc->fused_args(step);
+            if (want_camera_grad) {
+                check(cugs_project_backward_adam_mcmc_pose(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
+                                                           ptr<float>(model.positions), ptr<float>(model.rotations),
+                                                           ptr<float>(model.scales), ptr<float>(model.opacities),
+                                                           ptr<float>(model.sh_coeffs), ptr<int32_t>(radii),
+                                                           ptr<uint8_t>(gate), &camera, settings.scale_modifier,
+                                                           ptr<float>(rb.grad_accum), &adam, &mc,
+                                                           ptr<float>(o.dL_dmeans_2d), &pose, stream_of(dL_dcolor)),
+                      "cugs_project_backward_adam_mcmc_pose");
+                return o;
+            }
             check(cugs_project_backward_adam_mcmc(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
                                                   ptr<float>(model.positions), ptr<float>(model.rotations),
                                                   ptr<float>(model.scales), ptr<float>(model.opacities),
@@ -568,6 +603,16 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                                                   &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam, &mc,
                                                   ptr<float>(o.dL_dmeans_2d), stream_of(dL_dcolor)),
                   "cugs_project_backward_adam_mcmc");
+            return o;
+        }
+        if (want_camera_grad) {
+            check(cugs_project_backward_adam_pose(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
+                                                  ptr<float>(model.positions), ptr<float>(model.rotations),
+                                                  ptr<float>(model.scales), ptr<float>(model.opacities),
+                                                  ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate),
+                                                  &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam,
+                                                  ptr<float>(o.dL_dmeans_2d), &pose, stream_of(dL_dcolor)),
+                  "cugs_project_backward_adam_pose");
             return o;
         }
         check(cugs_project_backward_adam(n, static_cast<int>(model.sh_coeffs.size(2)), degree, ptr<float>(model.positions),
@@ -583,7 +628,7 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
     const bool have_gate = ro.colour_gate.defined() && ro.colour_gate.dim() == 1 && ro.colour_gate.size(0) == n;
     auto pb = project_backward_impl(&rb.grad_accum, have_gate ? &ro.colour_gate : nullptr, &o.dL_dmeans_2d, {}, {}, {}, {}, model.positions,
                                     model.rotations, model.scales, model.opacities, model.sh_coeffs, ro.radii, camera, degree,
-                                    settings.scale_modifier);
+                                    settings.scale_modifier, want_camera_grad ? &pose : nullptr);
     o.dL_dpositions = pb.dL_dpositions; o.dL_drotations = pb.dL_drotations; o.dL_dscales = pb.dL_dscales;
     o.dL_dopacities = pb.dL_dopacities; o.dL_dsh_coeffs = pb.dL_dsh_coeffs;
     return o;

@@ -61,7 +61,12 @@ struct RenderOutput {              // rasterizer/rasterizer.hpp:27-46
     // The alpha (coverage) map is 1 - final_T; depth_map / alpha is the normalised depth.
     torch::Tensor depth_map;
 };
-struct BackwardOutput { torch::Tensor dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs, dL_dmeans_2d; };
+// dL_dviewmat (not in the reference): [4,4] dL/d(world-to-camera matrix), render_backward(...,
+// want_camera_grad = true) only, undefined otherwise.
+struct BackwardOutput {
+    torch::Tensor dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs, dL_dmeans_2d;
+    torch::Tensor dL_dviewmat;
+};
 
 ProjectionOutput project_gaussians(const torch::Tensor& positions, const torch::Tensor& rotations,
                                    const torch::Tensor& scales, const torch::Tensor& opacities,
@@ -111,12 +116,16 @@ class MCMCController;
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& render_out,
                                const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
                                FusedAdam* fused = nullptr, const MCMCController* mcmc = nullptr, int step = 0,
-                               const torch::Tensor& dL_ddepth_map = {}, const torch::Tensor& dL_dalpha = {});
+                               const torch::Tensor& dL_ddepth_map = {}, const torch::Tensor& dL_dalpha = {},
+                               bool want_camera_grad = false);
 // `mcmc` (with `fused` only): the regulariser gradient and the position noise of iteration `step` ride in
 // the same launch (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + compute_regularization's
 // gradients, apply_gradients, step, inject_noise(model, step).
 // `dL_ddepth_map`, `dL_dalpha` ([H,W] each, optional, not in the reference): the gradients of RenderOutput::depth_map
 // (needs render(..., want_depth_map = true)) and of the alpha map 1 - final_T, on every route above.
+// `want_camera_grad` (not in the reference): BackwardOutput::dL_dviewmat, the gradient with respect to
+// camera.view (row 3 zero; the SH view direction held constant), on every route above, with no host sync; every other
+// output is unchanged, bit for bit.
 
 // training/loss.hpp:21-52 + the autograd step of trainer.cpp:214-217 in two launches.
 // Scalars are 0-dim device tensors, as in the reference.

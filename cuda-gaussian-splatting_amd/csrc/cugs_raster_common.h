@@ -353,3 +353,27 @@ __device__ __forceinline__ float reduce10r16(float cA, float cB, float v2, float
         : "v"(cA), "v"(cB), "v"(v2), "v"(v3), "v"(v4), "v"(v5), "v"(v6), "v"(v8), "v"(v7), "v"(v9));
     return reduce_r16_tail(b0, b1, b2, lane);
 }
+
+// reduce12r16: the transpose-reduce of TWELVE per-lane values inside each 16-lane DPP row (the camera-pose backward's
+// per-Gaussian rows, project_backward_kernels.h), in plain builtins - it runs once per workgroup, not per blend step, so
+// the selects cost nothing that matters.  Stage 1 row_mirror (side = lane bit 3): 12 -> 6; stage 2 row_half_mirror
+// (bit 2): 6 -> 3; stage 3 quad_perm [2,3,0,1] (bit 1): 3 -> 2 (values 0 | 1 exchanged, value 2 summed by both);
+// stage 4 quad_perm [1,0,3,2] (bit 0): 2 -> 1.  The partners of the four stages are lane ^ 15, ^ 7, ^ 2, ^ 1, which
+// together reach all sixteen lanes of the row.  All 64 lanes must be active.
+// Result, per row: lane r returns the ROW total of slot reduce12r16_slot(r) = (r&1 ? 2 : (r>>1)&1) + 3*((r>>2)&1) +
+// 6*((r>>3)&1); lanes with r&3 == 3 hold a second copy of a slot (-1: not designated).
+__device__ __forceinline__ int reduce12r16_slot(int lane) {
+    const int r = lane & 15;
+    if ((r & 3) == 3) return -1;
+    return ((r & 1) ? 2 : ((r >> 1) & 1)) + 3 * ((r >> 2) & 1) + 6 * ((r >> 3) & 1);
+}
+
+__device__ __forceinline__ float reduce12r16(const float (&v)[12], int lane) {
+    const bool s3 = (lane & 8) != 0, s2 = (lane & 4) != 0;
+    float u[6], w[3];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) u[k] = xchg_add<0x140>(s3, v[k], v[k + 6]);       // row_mirror
+#pragma unroll
+    for (int k = 0; k < 3; ++k) w[k] = xchg_add<0x141>(s2, u[k], u[k + 3]);       // row_half_mirror
+    return reduce_r16_tail(w[0], w[1], w[2], lane);                                // quad_perm stages
+}

@@ -37,26 +37,26 @@ int launch_pb(int64_t n, int degree, const CamArgs& cam, const PBPtrs& p, bool a
     if (adam) {
         if constexpr (C == 16) {
             if (aligned && p.colour_gate) {
-                hipLaunchKernelGGL((k_project_backward<C, true, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{});
+                hipLaunchKernelGGL((k_project_backward<C, true, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{}, PoseArgs{});
                 CUGS_LAUNCH_CHECK();
                 return 0;
             }
         }
         if (aligned)
-            hipLaunchKernelGGL((k_project_backward<C, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{});
+            hipLaunchKernelGGL((k_project_backward<C, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{}, PoseArgs{});
         else
-            hipLaunchKernelGGL((k_project_backward<C, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{});
+            hipLaunchKernelGGL((k_project_backward<C, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{}, PoseArgs{});
     } else if (aligned) {
         if constexpr (C == 16) {
             if (p.colour_gate) {
-                hipLaunchKernelGGL((k_project_backward<C, true, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{});
+                hipLaunchKernelGGL((k_project_backward<C, true, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{}, PoseArgs{});
                 CUGS_LAUNCH_CHECK();
                 return 0;
             }
         }
-        hipLaunchKernelGGL((k_project_backward<C, true, false>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{});
+        hipLaunchKernelGGL((k_project_backward<C, true, false>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{}, PoseArgs{});
     } else {
-        hipLaunchKernelGGL((k_project_backward<C, false, false>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{});
+        hipLaunchKernelGGL((k_project_backward<C, false, false>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{}, PoseArgs{});
     }
     CUGS_LAUNCH_CHECK();
     return 0;
@@ -86,25 +86,14 @@ extern "C" int cugs_project_backward(int64_t n, int num_coeffs, int active_degre
                                      const float* dL_dopacity_act, float* dL_dpositions, float* dL_drotations,
                                      float* dL_dscales, float* dL_dopacities, float* dL_dsh_coeffs,
                                      float* dL_dmeans_2d_out, float* dL_drgb_gated_out, void* stream) {
-    if (n < 0 || !camera_host) return CUGS_EINVAL;
-    if (active_degree < 0 || active_degree > 3) return CUGS_EINVAL;
-    if ((active_degree + 1) * (active_degree + 1) > num_coeffs) return CUGS_EINVAL;
-    if (num_coeffs != 1 && num_coeffs != 4 && num_coeffs != 9 && num_coeffs != 16) return CUGS_EINVAL;
-    if (n == 0) return 0;
-    if (!positions || !rotations || !scales || !opacities || !radii || !dL_dpositions || !dL_drotations ||
-        !dL_dscales || !dL_dopacities)
-        return CUGS_EINVAL;
-    // dL_dsh_coeffs and dL_drgb_gated_out both NULL: geometry gradients only (cugs_gated_colour_grad took the colour half)
-    if (!colour_gate && !sh_coeffs) return CUGS_EINVAL;
-    if (!grad_accum && (!dL_dmeans_2d || !dL_dcov_2d_inv || !dL_drgb || !dL_dopacity_act)) return CUGS_EINVAL;
-    if (grad_accum && !cugs_aligned16(grad_accum)) return CUGS_EALIGN;
-    const CamArgs cam = cugs_make_cam_args(camera_host, scale_modifier);
-    PBPtrs p{positions, rotations, scales, opacities, sh_coeffs, radii, colour_gate, grad_accum,
-             dL_dmeans_2d, dL_dcov_2d_inv, dL_drgb, dL_dopacity_act, dL_dpositions, dL_drotations,
-             dL_dscales, dL_dopacities, dL_dsh_coeffs, dL_dmeans_2d_out, dL_drgb_gated_out,
-             nullptr, nullptr, nullptr, nullptr, nullptr};
-    const bool aligned = (!dL_dsh_coeffs || cugs_aligned16(dL_dsh_coeffs)) && cugs_aligned16(rotations) && cugs_aligned16(dL_drotations) &&
-                         (colour_gate || cugs_aligned16(sh_coeffs));
+    CamArgs cam;
+    PBPtrs p;
+    bool aligned;
+    const int r = prepare_plain(n, num_coeffs, active_degree, positions, rotations, scales, opacities, sh_coeffs, radii,
+                                colour_gate, camera_host, scale_modifier, grad_accum, dL_dmeans_2d, dL_dcov_2d_inv, dL_drgb,
+                                dL_dopacity_act, dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs,
+                                dL_dmeans_2d_out, dL_drgb_gated_out, cam, p, aligned);
+    if (r != 0) return r == 1 ? 0 : r;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (num_coeffs) {
         case 1: return launch_pb<1>(n, active_degree, cam, p, aligned, st);

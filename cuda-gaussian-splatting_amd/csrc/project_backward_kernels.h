@@ -4,7 +4,7 @@
 // of k_project_backward live in the second one: compiled into the same module they changed the register allocation
 // of the existing ADAM instantiations; apart, those compile to the same code as without N5.
 #pragma once
-#include "cugs_gaussian_math.h"
+#include "cugs_raster_common.h"
 #include "cugs_mcmc.h"
 
 namespace {
@@ -271,13 +271,16 @@ __device__ __forceinline__ float4 grad_quat(const QuatRot& q, const M3& g) {
                        q.inv_norm * (dy - y * dot), q.inv_norm * (dz - z * dot));
 }
 
-// Contribution of Sigma' to dL/dt through J(t) (backward.cuh:248-346); adds into dt.
+// Contribution of Sigma' to dL/dt through J(t) (backward.cuh:248-346); adds into dt.  K receives k0..k5 = dL/dT for
+// T = J W (row-major 2x3), which the camera-pose route (POSE) turns into dL/dW = J^T K.
 __device__ __forceinline__ void add_grad_t_from_cov(const Sym2& g, const Sym3& S, const M3& W, V3 t,
-                                                    float fx, float fy, const Jac& J, const M23& T, V3& dt) {
+                                                    float fx, float fy, const Jac& J, const M23& T, V3& dt,
+                                                    float (&K)[6]) {
     const M23 TS = times_sym3(T, S);
     const float k0 = 2.0f * (g.a * TS.r0x + g.b * TS.r1x), k1 = 2.0f * (g.a * TS.r0y + g.b * TS.r1y);
     const float k2 = 2.0f * (g.a * TS.r0z + g.b * TS.r1z), k3 = 2.0f * (g.b * TS.r0x + g.c * TS.r1x);
     const float k4 = 2.0f * (g.b * TS.r0y + g.c * TS.r1y), k5 = 2.0f * (g.b * TS.r0z + g.c * TS.r1z);
+    K[0] = k0; K[1] = k1; K[2] = k2; K[3] = k3; K[4] = k4; K[5] = k5;
     const float j0 = k0 * W.m00 + k1 * W.m01 + k2 * W.m02;     // dL/dJ[0][0]
     const float j2 = k0 * W.m20 + k1 * W.m21 + k2 * W.m22;     // dL/dJ[0][2]
     const float j4 = k3 * W.m10 + k4 * W.m11 + k5 * W.m12;     // dL/dJ[1][1]
@@ -300,6 +303,34 @@ struct PBPtrs {
     float* w_pos; float* w_rot; float* w_scl; float* w_opa; float* w_sh;
 };
 
+// POSE variant only (project_backward_pose.hip): where the camera gradient goes.
+struct PoseArgs {
+    float* partial;     // [gridDim.x, 12] one fp32 partial per workgroup: dL/dW row-major, then dL/dtvec
+    float* rows;        // [n, 12] the per-Gaussian terms (tests), or NULL
+};
+constexpr int POSE_TERMS = 12;
+
+// The workgroup's sum of the twelve per-thread camera terms -> out[0..11]: reduce12r16 inside each DPP row, the four
+// rows of a wave by two xor shuffles, the CUGS_BLOCK / 64 waves through LDS in wave order.  `s_red` is the SH tile,
+// free once every thread has passed the barrier at the top (its last reader, the SH gradient rows, is done).  A fixed
+// tree: the same bits whatever order the waves run in.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void pose_block_partial(const float (&v)[POSE_TERMS], float* s_red, float* __restrict__ out) {
+    const int lane = (int)threadIdx.x & (CUGS_WAVE - 1), wave = (int)threadIdx.x / CUGS_WAVE;
+    float r = reduce12r16(v, lane);
+    r += __shfl_xor(r, 16);
+    r += __shfl_xor(r, 32);
+    __syncthreads();
+    const int slot = reduce12r16_slot(lane);
+    if (lane < 16 && slot >= 0) s_red[wave * POSE_TERMS + slot] = r;
+    __syncthreads();
+    if (threadIdx.x < POSE_TERMS) {
+        float acc = s_red[threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < CUGS_BLOCK / CUGS_WAVE; ++w) acc += s_red[w * POSE_TERMS + threadIdx.x];
+        out[threadIdx.x] = acc;
+    }
+}
+
 // ADAM: instead of writing the five parameter gradients, apply the Adam update to this Gaussian's parameters in
 // the same pass (every thread touches only its own Gaussian; the SH block goes through the LDS tile): 236 B/Gaussian
 // of gradient writes and as many reads by a separate optimizer launch disappear (472 of 2020 B at degree 3).
@@ -309,9 +340,13 @@ struct PBPtrs {
 // regulariser gradient joins d_logit / d_log of every live Gaussian (radius 0 included: the reference adds it to the
 // whole gradient tensor), opacity and scales are stepped before the position, and the position noise, formed from the
 // UPDATED opacity and scales as cugs_mcmc_inject_noise forms it, joins the updated position.
-template <int C, bool ALIGNED, bool ADAM, bool FACTORS = false, bool MCMC = false>
+// POSE (project_backward_pose.hip): every live Gaussian also forms its share of the camera gradient, dL/dW = dt (x) p +
+// J^T K and dL/dtvec = dt (zeros where the geometry branch does not run), and the workgroup writes their sum to
+// pose.partial[blockIdx.x] (pose_block_partial); pose.rows, when given, receives each Gaussian's twelve terms.  Dead
+// lanes stay to the end for the workgroup's barriers.  Everything else it computes is what the variant without it does.
+template <int C, bool ALIGNED, bool ADAM, bool FACTORS = false, bool MCMC = false, bool POSE = false>
 __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int degree, CamArgs cam, PBPtrs p,
-                                                                AdamFusedArgs adam, McmcFusedArgs mc) {
+                                                                AdamFusedArgs adam, McmcFusedArgs mc, PoseArgs pose) {
     static_assert(!MCMC || ADAM, "the MCMC route is the fused optimizer step's");
     static_assert(!FACTORS || (C == 16 && ALIGNED), "factor tile: degree-3 storage, 16-byte rows");
     constexpr int LROW = FACTORS ? SH_FACTOR_ROW : ShTile<C>::LROW;
@@ -405,134 +440,155 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
         if (ADAM) adam_sh_rows<C, ALIGNED>(p.w_sh, adam.m[1], adam.v[1], base, count, s_sh, adam.lr[1], adam);
         else store_sh_rows<C, ALIGNED>(p.d_sh, base, count, s_sh);
     }
-    if (!live) return;
+    if (!POSE && !live) return;
+    float pg[POSE_TERMS];                                     // POSE: this Gaussian's camera terms
+#pragma unroll
+    for (int k = 0; k < POSE_TERMS; ++k) pg[k] = 0.0f;
 
-    // ---- geometry ----
-    V3 d_pos{0.0f, 0.0f, 0.0f}, d_log{0.0f, 0.0f, 0.0f};
-    float4 d_q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float d_logit = 0.0f;
-    if ((FACTORS ? in_radius : p.radii[idx]) > 0) {            // projection_backward.cu:48
-        const M3 W = view_rotation(cam);
-        const V3 t = to_camera(cam, W, pos);
-        if (!FACTORS) {
-            in_scl[0] = ldp(p.scales + idx * 3 + 0); in_scl[1] = ldp(p.scales + idx * 3 + 1); in_scl[2] = ldp(p.scales + idx * 3 + 2);
-        }
-        const V3 s{cugs_expf(in_scl[0] + cam.log_mod), cugs_expf(in_scl[1] + cam.log_mod), cugs_expf(in_scl[2] + cam.log_mod)};
-        const float4 q = FACTORS ? in_q
-                       : ALIGNED ? (ADAM ? reinterpret_cast<const float4*>(p.rotations)[idx]
-                                         : cugs_ldnt(reinterpret_cast<const float4*>(p.rotations) + idx))
-                                 : make_float4(p.rotations[idx * 4 + 0], p.rotations[idx * 4 + 1],
-                                               p.rotations[idx * 4 + 2], p.rotations[idx * 4 + 3]);
-        const QuatRot qr = rotation_of(q.x, q.y, q.z, q.w);
-        const M3 M = scale_columns(qr.R, s);
-        const Sym3 S = gram(M);
-        const Jac J = jacobian(t, cam.fx, cam.fy);
-        const Sym2 cov = screen_covariance(project_matrix_full(J, W), S);
-        Sym2 inv;
-        if (invert_sym2(cov, inv) > 0.0f) {                    // projection_backward.cu:91
-            if (from_rows) {                                   // a Gaussian with a non-zero row passed this test in the forward
-                const Grad2D g2 = grads_from_moments(mom, inv.a, inv.b, inv.c);
-                g_mx = g2.mx; g_my = g2.my;
-                g_inv = Sym2{g2.a, g2.b, g2.c};
+    if (live) {
+        // ---- geometry ----
+        V3 d_pos{0.0f, 0.0f, 0.0f}, d_log{0.0f, 0.0f, 0.0f};
+        float4 d_q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float d_logit = 0.0f;
+        if ((FACTORS ? in_radius : p.radii[idx]) > 0) {            // projection_backward.cu:48
+            const M3 W = view_rotation(cam);
+            const V3 t = to_camera(cam, W, pos);
+            if (!FACTORS) {
+                in_scl[0] = ldp(p.scales + idx * 3 + 0); in_scl[1] = ldp(p.scales + idx * 3 + 1); in_scl[2] = ldp(p.scales + idx * 3 + 2);
             }
-            const M23 T = project_matrix_sparse(J, W);
-            const Sym2 g_cov = grad_cov_from_inv(inv, g_inv);
-            const Sym3 g_S = grad_cov3d(T, g_cov);
-            const M3 g_M = grad_M(g_S, M);
-            // M = R diag(s): dL/dR_ij = dL/dM_ij s_j; dL/ds_j = sum_i dL/dM_ij R_ij; x s_j for log-space
-            const M3 g_R{g_M.m00 * s.x, g_M.m01 * s.y, g_M.m02 * s.z, g_M.m10 * s.x, g_M.m11 * s.y,
-                         g_M.m12 * s.z, g_M.m20 * s.x, g_M.m21 * s.y, g_M.m22 * s.z};
-            const M3& R = qr.R;
-            d_log.x = (g_M.m00 * R.m00 + g_M.m10 * R.m10 + g_M.m20 * R.m20) * s.x;
-            d_log.y = (g_M.m01 * R.m01 + g_M.m11 * R.m11 + g_M.m21 * R.m21) * s.y;
-            d_log.z = (g_M.m02 * R.m02 + g_M.m12 * R.m12 + g_M.m22 * R.m22) * s.z;
-            d_q = grad_quat(qr, g_R);
+            const V3 s{cugs_expf(in_scl[0] + cam.log_mod), cugs_expf(in_scl[1] + cam.log_mod), cugs_expf(in_scl[2] + cam.log_mod)};
+            const float4 q = FACTORS ? in_q
+                           : ALIGNED ? (ADAM ? reinterpret_cast<const float4*>(p.rotations)[idx]
+                                             : cugs_ldnt(reinterpret_cast<const float4*>(p.rotations) + idx))
+                                     : make_float4(p.rotations[idx * 4 + 0], p.rotations[idx * 4 + 1],
+                                                   p.rotations[idx * 4 + 2], p.rotations[idx * 4 + 3]);
+            const QuatRot qr = rotation_of(q.x, q.y, q.z, q.w);
+            const M3 M = scale_columns(qr.R, s);
+            const Sym3 S = gram(M);
+            const Jac J = jacobian(t, cam.fx, cam.fy);
+            const Sym2 cov = screen_covariance(project_matrix_full(J, W), S);
+            Sym2 inv;
+            if (invert_sym2(cov, inv) > 0.0f) {                    // projection_backward.cu:91
+                if (from_rows) {                                   // a Gaussian with a non-zero row passed this test in the forward
+                    const Grad2D g2 = grads_from_moments(mom, inv.a, inv.b, inv.c);
+                    g_mx = g2.mx; g_my = g2.my;
+                    g_inv = Sym2{g2.a, g2.b, g2.c};
+                }
+                const M23 T = project_matrix_sparse(J, W);
+                const Sym2 g_cov = grad_cov_from_inv(inv, g_inv);
+                const Sym3 g_S = grad_cov3d(T, g_cov);
+                const M3 g_M = grad_M(g_S, M);
+                // M = R diag(s): dL/dR_ij = dL/dM_ij s_j; dL/ds_j = sum_i dL/dM_ij R_ij; x s_j for log-space
+                const M3 g_R{g_M.m00 * s.x, g_M.m01 * s.y, g_M.m02 * s.z, g_M.m10 * s.x, g_M.m11 * s.y,
+                             g_M.m12 * s.z, g_M.m20 * s.x, g_M.m21 * s.y, g_M.m22 * s.z};
+                const M3& R = qr.R;
+                d_log.x = (g_M.m00 * R.m00 + g_M.m10 * R.m10 + g_M.m20 * R.m20) * s.x;
+                d_log.y = (g_M.m01 * R.m01 + g_M.m11 * R.m11 + g_M.m21 * R.m21) * s.y;
+                d_log.z = (g_M.m02 * R.m02 + g_M.m12 * R.m12 + g_M.m22 * R.m22) * s.z;
+                d_q = grad_quat(qr, g_R);
 
-            V3 dt{0.0f, 0.0f, 0.0f};                            // projection_backward.cu:194-199
-            dt.x += g_mx * cam.fx * J.tz_inv;
-            dt.y += g_my * cam.fy * J.tz_inv;
-            dt.z += g_mx * (-cam.fx * t.x * J.tz_inv2) + g_my * (-cam.fy * t.y * J.tz_inv2);
-            add_grad_t_from_cov(g_cov, S, W, t, cam.fx, cam.fy, J, T, dt);
-            dt.z = (g_z != 0.0f) ? dt.z + g_z : dt.z;           // depth map: z = t.z; a zero word leaves every bit
-            d_pos.x = W.m00 * dt.x + W.m10 * dt.y + W.m20 * dt.z;
-            d_pos.y = W.m01 * dt.x + W.m11 * dt.y + W.m21 * dt.z;
-            d_pos.z = W.m02 * dt.x + W.m12 * dt.y + W.m22 * dt.z;
+                V3 dt{0.0f, 0.0f, 0.0f};                            // projection_backward.cu:194-199
+                dt.x += g_mx * cam.fx * J.tz_inv;
+                dt.y += g_my * cam.fy * J.tz_inv;
+                dt.z += g_mx * (-cam.fx * t.x * J.tz_inv2) + g_my * (-cam.fy * t.y * J.tz_inv2);
+                float K[6];
+                add_grad_t_from_cov(g_cov, S, W, t, cam.fx, cam.fy, J, T, dt, K);
+                dt.z = (g_z != 0.0f) ? dt.z + g_z : dt.z;           // depth map: z = t.z; a zero word leaves every bit
+                if (POSE) {                                         // t = W p + tvec, T = J W
+                    pg[0] = dt.x * pos.x + J.j00 * K[0]; pg[1] = dt.x * pos.y + J.j00 * K[1]; pg[2] = dt.x * pos.z + J.j00 * K[2];
+                    pg[3] = dt.y * pos.x + J.j11 * K[3]; pg[4] = dt.y * pos.y + J.j11 * K[4]; pg[5] = dt.y * pos.z + J.j11 * K[5];
+                    pg[6] = dt.z * pos.x + (J.j02 * K[0] + J.j12 * K[3]);
+                    pg[7] = dt.z * pos.y + (J.j02 * K[1] + J.j12 * K[4]);
+                    pg[8] = dt.z * pos.z + (J.j02 * K[2] + J.j12 * K[5]);
+                    pg[9] = dt.x; pg[10] = dt.y; pg[11] = dt.z;
+                }
+                d_pos.x = W.m00 * dt.x + W.m10 * dt.y + W.m20 * dt.z;
+                d_pos.y = W.m01 * dt.x + W.m11 * dt.y + W.m21 * dt.z;
+                d_pos.z = W.m02 * dt.x + W.m12 * dt.y + W.m22 * dt.z;
 
-            const float sig = cugs_sigmoidf(FACTORS ? in_opa : ldp(p.opacities + idx));
-            d_logit = g_opa * sig * (1.0f - sig);
+                const float sig = cugs_sigmoidf(FACTORS ? in_opa : ldp(p.opacities + idx));
+                d_logit = g_opa * sig * (1.0f - sig);
+            }
         }
+        if (MCMC) {
+            // the regulariser on the parameters as they were before this step (compute_regularization runs before it)
+            float opa_new, scl_new[3];
+            {
+                float w = p.w_opa[idx], m = adam.m[2][idx], v = adam.v[2][idx];
+                adam_update(w, d_logit + cugs_mcmc_reg_opacity(mc.coef_o, w), m, v, adam.lr[2], adam);
+                p.w_opa[idx] = w; adam.m[2][idx] = m; adam.v[2][idx] = v;
+                opa_new = w;
+            }
+            const float gs[3] = {d_log.x, d_log.y, d_log.z};
+    #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float w = p.w_scl[idx * 3 + k], m = adam.m[3][idx * 3 + k], v = adam.v[3][idx * 3 + k];
+                adam_update(w, gs[k] + cugs_mcmc_reg_scale(mc.coef_s, w), m, v, adam.lr[3], adam);
+                p.w_scl[idx * 3 + k] = w; adam.m[3][idx * 3 + k] = m; adam.v[3][idx * 3 + k] = v;
+                scl_new[k] = w;
+            }
+            float z[3];
+            if (mc.noise) { z[0] = mc.noise[idx * 3 + 0]; z[1] = mc.noise[idx * 3 + 1]; z[2] = mc.noise[idx * 3 + 2]; }
+            else cugs_mcmc_normals3(mc.seed, CUGS_MCMC_STREAM_NOISE, mc.step, (uint64_t)idx, z);
+            const float gate = cugs_mcmc_gate(opa_new, mc.gate_k, mc.gate_t);
+            const float gp[3] = {d_pos.x, d_pos.y, d_pos.z};
+    #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float w = p.w_pos[idx * 3 + k], m = adam.m[0][idx * 3 + k], v = adam.v[0][idx * 3 + k];
+                adam_update(w, gp[k], m, v, adam.lr[0], adam);
+                p.w_pos[idx * 3 + k] = cugs_mcmc_noisy(w, scl_new[k], gate, mc.noise_lr, z[k]);
+                adam.m[0][idx * 3 + k] = m; adam.v[0][idx * 3 + k] = v;
+            }
+            const float gq[4] = {d_q.x, d_q.y, d_q.z, d_q.w};
+    #pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float w = p.w_rot[idx * 4 + k], m = adam.m[4][idx * 4 + k], v = adam.v[4][idx * 4 + k];
+                adam_update(w, gq[k], m, v, adam.lr[4], adam);
+                p.w_rot[idx * 4 + k] = w; adam.m[4][idx * 4 + k] = m; adam.v[4][idx * 4 + k] = v;
+            }
+        } else if (ADAM) {
+            const float gp[3] = {d_pos.x, d_pos.y, d_pos.z}, gs[3] = {d_log.x, d_log.y, d_log.z};
+            const float gq[4] = {d_q.x, d_q.y, d_q.z, d_q.w};
+    #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float w = p.w_pos[idx * 3 + k], m = adam.m[0][idx * 3 + k], v = adam.v[0][idx * 3 + k];
+                adam_update(w, gp[k], m, v, adam.lr[0], adam);
+                p.w_pos[idx * 3 + k] = w; adam.m[0][idx * 3 + k] = m; adam.v[0][idx * 3 + k] = v;
+            }
+            {
+                float w = p.w_opa[idx], m = adam.m[2][idx], v = adam.v[2][idx];
+                adam_update(w, d_logit, m, v, adam.lr[2], adam);
+                p.w_opa[idx] = w; adam.m[2][idx] = m; adam.v[2][idx] = v;
+            }
+    #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float w = p.w_scl[idx * 3 + k], m = adam.m[3][idx * 3 + k], v = adam.v[3][idx * 3 + k];
+                adam_update(w, gs[k], m, v, adam.lr[3], adam);
+                p.w_scl[idx * 3 + k] = w; adam.m[3][idx * 3 + k] = m; adam.v[3][idx * 3 + k] = v;
+            }
+    #pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float w = p.w_rot[idx * 4 + k], m = adam.m[4][idx * 4 + k], v = adam.v[4][idx * 4 + k];
+                adam_update(w, gq[k], m, v, adam.lr[4], adam);
+                p.w_rot[idx * 4 + k] = w; adam.m[4][idx * 4 + k] = m; adam.v[4][idx * 4 + k] = v;
+            }
+        } else {
+            // the gradients are next read by the optimizer (or the exchange), a frame's worth of traffic later
+            cugs_stnt(p.d_pos + idx * 3 + 0, d_pos.x); cugs_stnt(p.d_pos + idx * 3 + 1, d_pos.y); cugs_stnt(p.d_pos + idx * 3 + 2, d_pos.z);
+            if (ALIGNED) cugs_stnt(reinterpret_cast<float4*>(p.d_rot) + idx, d_q);
+            else { p.d_rot[idx * 4 + 0] = d_q.x; p.d_rot[idx * 4 + 1] = d_q.y; p.d_rot[idx * 4 + 2] = d_q.z; p.d_rot[idx * 4 + 3] = d_q.w; }
+            cugs_stnt(p.d_scl + idx * 3 + 0, d_log.x); cugs_stnt(p.d_scl + idx * 3 + 1, d_log.y); cugs_stnt(p.d_scl + idx * 3 + 2, d_log.z);
+            cugs_stnt(p.d_opa + idx, d_logit);
+        }
+        if (p.d_means_out) { p.d_means_out[idx * 2 + 0] = g_mx; p.d_means_out[idx * 2 + 1] = g_my; }
     }
-    if (MCMC) {
-        // the regulariser on the parameters as they were before this step (compute_regularization runs before it)
-        float opa_new, scl_new[3];
-        {
-            float w = p.w_opa[idx], m = adam.m[2][idx], v = adam.v[2][idx];
-            adam_update(w, d_logit + cugs_mcmc_reg_opacity(mc.coef_o, w), m, v, adam.lr[2], adam);
-            p.w_opa[idx] = w; adam.m[2][idx] = m; adam.v[2][idx] = v;
-            opa_new = w;
-        }
-        const float gs[3] = {d_log.x, d_log.y, d_log.z};
+    if constexpr (POSE) {
+        if (live && pose.rows) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float w = p.w_scl[idx * 3 + k], m = adam.m[3][idx * 3 + k], v = adam.v[3][idx * 3 + k];
-            adam_update(w, gs[k] + cugs_mcmc_reg_scale(mc.coef_s, w), m, v, adam.lr[3], adam);
-            p.w_scl[idx * 3 + k] = w; adam.m[3][idx * 3 + k] = m; adam.v[3][idx * 3 + k] = v;
-            scl_new[k] = w;
+            for (int k = 0; k < POSE_TERMS; ++k) pose.rows[idx * POSE_TERMS + k] = pg[k];
         }
-        float z[3];
-        if (mc.noise) { z[0] = mc.noise[idx * 3 + 0]; z[1] = mc.noise[idx * 3 + 1]; z[2] = mc.noise[idx * 3 + 2]; }
-        else cugs_mcmc_normals3(mc.seed, CUGS_MCMC_STREAM_NOISE, mc.step, (uint64_t)idx, z);
-        const float gate = cugs_mcmc_gate(opa_new, mc.gate_k, mc.gate_t);
-        const float gp[3] = {d_pos.x, d_pos.y, d_pos.z};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float w = p.w_pos[idx * 3 + k], m = adam.m[0][idx * 3 + k], v = adam.v[0][idx * 3 + k];
-            adam_update(w, gp[k], m, v, adam.lr[0], adam);
-            p.w_pos[idx * 3 + k] = cugs_mcmc_noisy(w, scl_new[k], gate, mc.noise_lr, z[k]);
-            adam.m[0][idx * 3 + k] = m; adam.v[0][idx * 3 + k] = v;
-        }
-        const float gq[4] = {d_q.x, d_q.y, d_q.z, d_q.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float w = p.w_rot[idx * 4 + k], m = adam.m[4][idx * 4 + k], v = adam.v[4][idx * 4 + k];
-            adam_update(w, gq[k], m, v, adam.lr[4], adam);
-            p.w_rot[idx * 4 + k] = w; adam.m[4][idx * 4 + k] = m; adam.v[4][idx * 4 + k] = v;
-        }
-    } else if (ADAM) {
-        const float gp[3] = {d_pos.x, d_pos.y, d_pos.z}, gs[3] = {d_log.x, d_log.y, d_log.z};
-        const float gq[4] = {d_q.x, d_q.y, d_q.z, d_q.w};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float w = p.w_pos[idx * 3 + k], m = adam.m[0][idx * 3 + k], v = adam.v[0][idx * 3 + k];
-            adam_update(w, gp[k], m, v, adam.lr[0], adam);
-            p.w_pos[idx * 3 + k] = w; adam.m[0][idx * 3 + k] = m; adam.v[0][idx * 3 + k] = v;
-        }
-        {
-            float w = p.w_opa[idx], m = adam.m[2][idx], v = adam.v[2][idx];
-            adam_update(w, d_logit, m, v, adam.lr[2], adam);
-            p.w_opa[idx] = w; adam.m[2][idx] = m; adam.v[2][idx] = v;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float w = p.w_scl[idx * 3 + k], m = adam.m[3][idx * 3 + k], v = adam.v[3][idx * 3 + k];
-            adam_update(w, gs[k], m, v, adam.lr[3], adam);
-            p.w_scl[idx * 3 + k] = w; adam.m[3][idx * 3 + k] = m; adam.v[3][idx * 3 + k] = v;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float w = p.w_rot[idx * 4 + k], m = adam.m[4][idx * 4 + k], v = adam.v[4][idx * 4 + k];
-            adam_update(w, gq[k], m, v, adam.lr[4], adam);
-            p.w_rot[idx * 4 + k] = w; adam.m[4][idx * 4 + k] = m; adam.v[4][idx * 4 + k] = v;
-        }
-    } else {
-        // the gradients are next read by the optimizer (or the exchange), a frame's worth of traffic later
-        cugs_stnt(p.d_pos + idx * 3 + 0, d_pos.x); cugs_stnt(p.d_pos + idx * 3 + 1, d_pos.y); cugs_stnt(p.d_pos + idx * 3 + 2, d_pos.z);
-        if (ALIGNED) cugs_stnt(reinterpret_cast<float4*>(p.d_rot) + idx, d_q);
-        else { p.d_rot[idx * 4 + 0] = d_q.x; p.d_rot[idx * 4 + 1] = d_q.y; p.d_rot[idx * 4 + 2] = d_q.z; p.d_rot[idx * 4 + 3] = d_q.w; }
-        cugs_stnt(p.d_scl + idx * 3 + 0, d_log.x); cugs_stnt(p.d_scl + idx * 3 + 1, d_log.y); cugs_stnt(p.d_scl + idx * 3 + 2, d_log.z);
-        cugs_stnt(p.d_opa + idx, d_logit);
+        pose_block_partial(pg, s_sh, pose.partial + (int64_t)blockIdx.x * POSE_TERMS);
     }
-    if (p.d_means_out) { p.d_means_out[idx * 2 + 0] = g_mx; p.d_means_out[idx * 2 + 1] = g_my; }
 }
 
 // ---- the gated colour gradient on its own (data-parallel exchange, early gather) ----
@@ -665,6 +721,47 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_sh_backward_views(int64_t n, int
 }
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + CUGS_BLOCK - 1) / CUGS_BLOCK); }
+
+// The argument checks and argument block of cugs_project_backward (and its POSE twin, project_backward_pose.hip).
+// Returns 1 when there is nothing to launch (n == 0), else 0 or a CUGS_E* code.
+inline int prepare_plain(int64_t n, int num_coeffs, int active_degree, const float* positions, const float* rotations,
+                         const float* scales, const float* opacities, const float* sh_coeffs, const int32_t* radii,
+                         const uint8_t* colour_gate, const cugs_camera* camera_host, float scale_modifier,
+                         const float* grad_accum, const float* dL_dmeans_2d, const float* dL_dcov_2d_inv,
+                         const float* dL_drgb, const float* dL_dopacity_act, float* dL_dpositions, float* dL_drotations,
+                         float* dL_dscales, float* dL_dopacities, float* dL_dsh_coeffs, float* dL_dmeans_2d_out,
+                         float* dL_drgb_gated_out, CamArgs& cam, PBPtrs& p, bool& aligned) {
+    if (n < 0 || !camera_host) return CUGS_EINVAL;
+    if (active_degree < 0 || active_degree > 3) return CUGS_EINVAL;
+    if ((active_degree + 1) * (active_degree + 1) > num_coeffs) return CUGS_EINVAL;
+    if (num_coeffs != 1 && num_coeffs != 4 && num_coeffs != 9 && num_coeffs != 16) return CUGS_EINVAL;
+    if (n == 0) return 1;
+    if (!positions || !rotations || !scales || !opacities || !radii || !dL_dpositions || !dL_drotations ||
+        !dL_dscales || !dL_dopacities)
+        return CUGS_EINVAL;
+    // dL_dsh_coeffs and dL_drgb_gated_out both NULL: geometry gradients only (cugs_gated_colour_grad took the colour half)
+    if (!colour_gate && !sh_coeffs) return CUGS_EINVAL;
+    if (!grad_accum && (!dL_dmeans_2d || !dL_dcov_2d_inv || !dL_drgb || !dL_dopacity_act)) return CUGS_EINVAL;
+    if (grad_accum && !cugs_aligned16(grad_accum)) return CUGS_EALIGN;
+    cam = cugs_make_cam_args(camera_host, scale_modifier);
+    p = PBPtrs{positions, rotations, scales, opacities, sh_coeffs, radii, colour_gate, grad_accum,
+               dL_dmeans_2d, dL_dcov_2d_inv, dL_drgb, dL_dopacity_act, dL_dpositions, dL_drotations,
+               dL_dscales, dL_dopacities, dL_dsh_coeffs, dL_dmeans_2d_out, dL_drgb_gated_out,
+               nullptr, nullptr, nullptr, nullptr, nullptr};
+    aligned = (!dL_dsh_coeffs || cugs_aligned16(dL_dsh_coeffs)) && cugs_aligned16(rotations) && cugs_aligned16(dL_drotations) &&
+              (colour_gate || cugs_aligned16(sh_coeffs));
+    return 0;
+}
+
+// The MCMC block of cugs_project_backward_adam_mcmc (and its POSE twin) for n > 0 Gaussians.
+inline int prepare_mcmc(int64_t n, const cugs_mcmc_fused* mcmc_host, McmcFusedArgs& mc) {
+    if (n > 2147483647ll / 3) return CUGS_EOVERFLOW;
+    mc.coef_o = mcmc_host->lambda_opacity / (float)n;            // the regulariser's mean, as cugs_mcmc_regularization
+    mc.coef_s = mcmc_host->lambda_scale / (float)(3 * n);
+    mc.noise_lr = mcmc_host->noise_lr; mc.gate_k = mcmc_host->gate_k; mc.gate_t = mcmc_host->gate_t;
+    mc.step = mcmc_host->step; mc.seed = mcmc_host->seed; mc.noise = mcmc_host->noise;
+    return 0;
+}
 
 // The argument checks and argument blocks of cugs_project_backward_adam / _mcmc (project_backward.hip,
 // project_backward_mcmc.hip).  Returns 1 when there is nothing to launch (n == 0), else 0 or a CUGS_E* code.

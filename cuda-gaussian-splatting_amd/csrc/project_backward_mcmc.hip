@@ -9,15 +9,15 @@ int launch_pb_mcmc(int64_t n, int degree, const CamArgs& cam, const PBPtrs& p, b
                    const AdamFusedArgs* adam, const McmcFusedArgs* mc) {
     if constexpr (C == 16) {
         if (aligned && p.colour_gate) {
-            hipLaunchKernelGGL((k_project_backward<C, true, true, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, *mc);
+            hipLaunchKernelGGL((k_project_backward<C, true, true, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, *mc, PoseArgs{});
             CUGS_LAUNCH_CHECK();
             return 0;
         }
     }
     if (aligned)
-        hipLaunchKernelGGL((k_project_backward<C, true, true, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, *mc);
+        hipLaunchKernelGGL((k_project_backward<C, true, true, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, *mc, PoseArgs{});
     else
-        hipLaunchKernelGGL((k_project_backward<C, false, true, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, *mc);
+        hipLaunchKernelGGL((k_project_backward<C, false, true, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, *mc, PoseArgs{});
     CUGS_LAUNCH_CHECK();
     return 0;
 }
@@ -40,12 +40,9 @@ extern "C" int cugs_project_backward_adam_mcmc(int64_t n, int num_coeffs, int ac
                                colour_gate, camera_host, scale_modifier, grad_accum, adam_host, dL_dmeans_2d_out, cam, p,
                                a, aligned);
     if (r != 0) return r == 1 ? 0 : r;
-    if (n > 2147483647ll / 3) return CUGS_EOVERFLOW;
     McmcFusedArgs mc;
-    mc.coef_o = mcmc_host->lambda_opacity / (float)n;            // the regulariser's mean, as cugs_mcmc_regularization
-    mc.coef_s = mcmc_host->lambda_scale / (float)(3 * n);
-    mc.noise_lr = mcmc_host->noise_lr; mc.gate_k = mcmc_host->gate_k; mc.gate_t = mcmc_host->gate_t;
-    mc.step = mcmc_host->step; mc.seed = mcmc_host->seed; mc.noise = mcmc_host->noise;
+    const int rm = prepare_mcmc(n, mcmc_host, mc);
+    if (rm != 0) return rm;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (num_coeffs) {
         case 1: return launch_pb_mcmc<1>(n, active_degree, cam, p, aligned, st, &a, &mc);

@@ -589,11 +589,19 @@ def project_backward(dL_dmeans_2d: Optional[torch.Tensor], dL_dcov_2d_inv: Optio
                      dL_dmeans_2d_out: Optional[torch.Tensor] = None,
                      dL_drgb_gated_out: Optional[torch.Tensor] = None,
                      skip_sh_grad: bool = False,
-                     geom_flat: Optional[torch.Tensor] = None) -> ProjectionBackwardOutput:
+                     geom_flat: Optional[torch.Tensor] = None, want_camera_grad: bool = False,
+                     dL_dview_rows: Optional[torch.Tensor] = None) -> ProjectionBackwardOutput:
+    """`want_camera_grad=True` (not in the reference): also the gradient with respect to the camera's
+    world-to-camera matrix, ProjectionBackwardOutput.dL_dviewmat [4,4] (row 3 zero; the SH view direction held constant,
+    as dL_dpositions holds it); every other output is unchanged, bit for bit.  `dL_dview_rows` ([N,12] float32, with
+    want_camera_grad, for tests): receives each Gaussian's terms, dL/dW row-major then dL/dtvec."""
     _torch_check(positions.is_cuda, "positions must be on CUDA")
     n = int(positions.shape[0])
     dev = positions.device
     f = dict(dtype=torch.float32, device=dev)
+    _torch_check(dL_dview_rows is None or want_camera_grad, "dL_dview_rows needs want_camera_grad=True")
+    _check_pose_rows(dL_dview_rows, n, dev)
+    d_view = torch.empty((4, 4), **f) if want_camera_grad else None
     if geom_flat is not None:      # one allocation [rot 4N | pos 3N | scl 3N | opa N]: all-reduced in place
         d_rot, d_pos, d_scl, d_opa = geometry_views(geom_flat, n)
     else:
@@ -602,19 +610,35 @@ def project_backward(dL_dmeans_2d: Optional[torch.Tensor], dL_dcov_2d_inv: Optio
     sh_c = _f32c(sh_coeffs)
     d_sh = None if skip_sh_grad else torch.empty_like(sh_c)      # skipped in the data-parallel exchange
     if n == 0:
-        return ProjectionBackwardOutput(d_pos, d_rot, d_scl, d_opa, d_sh)
+        if d_view is not None:
+            d_view.zero_()
+        return ProjectionBackwardOutput(d_pos, d_rot, d_scl, d_opa, d_sh, dL_dviewmat=d_view)
     pos_c, rot_c, scl_c, opa_c = map(_f32c, (positions, rotations, scales, opacities))
     cam = camera.to_abi()
     cont = lambda t: None if t is None else t.contiguous()
-    check(lib.cugs_project_backward(n, int(sh_c.shape[2]), int(active_sh_degree), _ptr(pos_c), _ptr(rot_c),
-                                    _ptr(scl_c), _ptr(opa_c), _ptr(sh_c), _ptr(radii.contiguous()),
-                                    _ptr(cont(colour_gate)), C.byref(cam), float(scale_modifier),
-                                    _ptr(cont(grad_accum)), _ptr(cont(dL_dmeans_2d)), _ptr(cont(dL_dcov_2d_inv)),
-                                    _ptr(cont(dL_drgb)), _ptr(cont(dL_dopacity_act)), _ptr(d_pos), _ptr(d_rot),
-                                    _ptr(d_scl), _ptr(d_opa), _ptr(d_sh), _ptr(dL_dmeans_2d_out),
-                                    _ptr(dL_drgb_gated_out), _stream(dev)),
-          "cugs_project_backward")
-    return ProjectionBackwardOutput(d_pos, d_rot, d_scl, d_opa, d_sh)
+    args = (n, int(sh_c.shape[2]), int(active_sh_degree), _ptr(pos_c), _ptr(rot_c), _ptr(scl_c), _ptr(opa_c), _ptr(sh_c),
+            _ptr(radii.contiguous()), _ptr(cont(colour_gate)), C.byref(cam), float(scale_modifier),
+            _ptr(cont(grad_accum)), _ptr(cont(dL_dmeans_2d)), _ptr(cont(dL_dcov_2d_inv)), _ptr(cont(dL_drgb)),
+            _ptr(cont(dL_dopacity_act)), _ptr(d_pos), _ptr(d_rot), _ptr(d_scl), _ptr(d_opa), _ptr(d_sh),
+            _ptr(dL_dmeans_2d_out), _ptr(dL_drgb_gated_out))
+    if want_camera_grad:
+        pg = _pose_grad(d_view, dL_dview_rows, n, dev)
+        check(lib.cugs_project_backward_pose(*args, C.byref(pg), _stream(dev)), "cugs_project_backward_pose")
+    else:
+        check(lib.cugs_project_backward(*args, _stream(dev)), "cugs_project_backward")
+    return ProjectionBackwardOutput(d_pos, d_rot, d_scl, d_opa, d_sh, dL_dviewmat=d_view)
+
+
+def _check_pose_rows(rows: Optional[torch.Tensor], n: int, dev) -> None:
+    _torch_check(rows is None or (tuple(rows.shape) == (n, 12) and rows.dtype == torch.float32 and rows.is_contiguous()
+                                  and rows.device == dev), "dL_dview_rows must be a contiguous [N, 12] float32 tensor")
+
+
+def _pose_grad(d_view: torch.Tensor, rows: Optional[torch.Tensor], n: int, dev) -> "_lib.PoseGrad":
+    """struct cugs_pose_grad over d_view ([4,4]) and a cached workspace (stream-ordered, like the sort's)."""
+    nbytes = int(lib.cugs_pose_grad_workspace_bytes(n))
+    ws = _workspace(dev, nbytes, kind="pose")
+    return _lib.PoseGrad(d_view.data_ptr(), None if rows is None else rows.data_ptr(), ws.data_ptr(), ws.numel())
 
 
 def geometry_views(flat: torch.Tensor, n: int):
@@ -734,7 +758,7 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                     geom_flat: Optional[torch.Tensor] = None, fused_adam=None, on_gated_ready=None,
                     mcmc=None, mcmc_step: int = 0, mcmc_noise: Optional[torch.Tensor] = None,
                     dL_ddepth_map: Optional[torch.Tensor] = None,
-                    dL_dalpha: Optional[torch.Tensor] = None) -> BackwardOutput:
+                    dL_dalpha: Optional[torch.Tensor] = None, want_camera_grad: bool = False) -> BackwardOutput:
     """`dL_drgb_gated_out` ([N,3], optional, not in the reference): when given, the per-view SH gradient
     is NOT materialised (dL_dsh_coeffs is None) and the gated colour gradient is written there instead,
     for parallel.exchange_gradients() to rebuild the summed SH gradient after the all-gather.
@@ -752,7 +776,13 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
     RenderOutput.depth_map (needs render(..., want_depth_map=True)) and of RenderOutput.alpha.  They reach the
     parameters through the blend (opacity, 2-D mean and covariance) and, for the depth map, through z = t.z
     (dL_dpositions += dL/dz W[2,:]); never the SH coefficients.  Plain and fused (fused_adam, mcmc) routes; the
-    data-parallel arguments are refused with them."""
+    data-parallel arguments are refused with them.
+    `want_camera_grad=True` (not in the reference): BackwardOutput.dL_dviewmat [4,4] float32 on the
+    device, the gradient with respect to camera.world_to_camera() (row 3 zero), from the same launch as the parameter
+    gradients (two small reduction launches follow it; no host sync).  The SH view direction is held constant, as it is
+    for dL_dpositions.  Plain and fused (fused_adam, mcmc) routes, with or without the depth / alpha map gradients; every
+    other output is unchanged, bit for bit; pose.viewmat_grad_to_se3 turns it into a 6-vector.  Not with the
+    data-parallel arguments."""
     _torch_check(dL_dcolor.is_cuda, "dL_dcolor must be on CUDA device")
     _torch_check(dL_dcolor.dim() == 3 and dL_dcolor.shape[2] == 3, "dL_dcolor must be [H, W, 3]")
     depth_grads = dL_ddepth_map is not None or dL_dalpha is not None
@@ -767,13 +797,18 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
         _torch_check(dL_drgb_gated_out is None and geom_flat is None and on_gated_ready is None,
                      "the depth / alpha map gradients are not supported with the data-parallel gradient exchange "
                      "(dL_drgb_gated_out, geom_flat, on_gated_ready)")
+    if want_camera_grad:
+        _torch_check(dL_drgb_gated_out is None and geom_flat is None and on_gated_ready is None,
+                     "the camera gradient is not supported with the data-parallel gradient exchange "
+                     "(dL_drgb_gated_out, geom_flat, on_gated_ready)")
     n = model.num_gaussians()
     dev = dL_dcolor.device
     f = dict(dtype=torch.float32, device=dev)
     if n == 0:                                           # rasterizer.cpp:130-139
         return BackwardOutput(torch.zeros((0, 3), **f), torch.zeros((0, 4), **f), torch.zeros((0, 3), **f),
                               torch.zeros((0, 1), **f), torch.zeros_like(model.sh_coeffs),
-                              torch.zeros((0, 2), **f))
+                              torch.zeros((0, 2), **f),
+                              dL_dviewmat=torch.zeros((4, 4), **f) if want_camera_grad else None)
     active_degree = min(int(settings.active_sh_degree), model.max_sh_degree())
     render_out.wait()                                    # a deferred render: read the pair count now (may raise)
     # the accumulator render() had the forward blend clear is good for ONE backward
@@ -807,13 +842,22 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                 _ptr(model.scales), _ptr(model.opacities), _ptr(model.sh_coeffs), _ptr(render_out.radii.contiguous()),
                 _ptr(render_out.colour_gate.contiguous()), C.byref(cam), float(settings.scale_modifier),
                 _ptr(rb.grad_accum), C.byref(adam))
+        d_view = torch.empty((4, 4), **f) if want_camera_grad else None
+        pg = _pose_grad(d_view, None, n, dev) if want_camera_grad else None
         if mcmc is not None:
             mc = mcmc.fused_args(mcmc_step, mcmc_noise)
-            check(lib.cugs_project_backward_adam_mcmc(*args, C.byref(mc), _ptr(d_means_2d), _stream(dev)),
-                  "cugs_project_backward_adam_mcmc")
+            if pg is not None:
+                check(lib.cugs_project_backward_adam_mcmc_pose(*args, C.byref(mc), _ptr(d_means_2d), C.byref(pg),
+                                                               _stream(dev)), "cugs_project_backward_adam_mcmc_pose")
+            else:
+                check(lib.cugs_project_backward_adam_mcmc(*args, C.byref(mc), _ptr(d_means_2d), _stream(dev)),
+                      "cugs_project_backward_adam_mcmc")
+        elif pg is not None:
+            check(lib.cugs_project_backward_adam_pose(*args, _ptr(d_means_2d), C.byref(pg), _stream(dev)),
+                  "cugs_project_backward_adam_pose")
         else:
             check(lib.cugs_project_backward_adam(*args, _ptr(d_means_2d), _stream(dev)), "cugs_project_backward_adam")
-        return BackwardOutput(None, None, None, None, None, d_means_2d)
+        return BackwardOutput(None, None, None, None, None, d_means_2d, dL_dviewmat=d_view)
     _torch_check(mcmc is None, "the fused MCMC route needs fused_adam (otherwise: compute_regularization, "
                  "step, inject_noise)")
     gated_by_projection = dL_drgb_gated_out
@@ -826,6 +870,7 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                           model.opacities, model.sh_coeffs, render_out.radii, camera, active_degree,
                           settings.scale_modifier, grad_accum=rb.grad_accum, colour_gate=render_out.colour_gate,
                           dL_dmeans_2d_out=d_means_2d, dL_drgb_gated_out=gated_by_projection,
-                          skip_sh_grad=dL_drgb_gated_out is not None, geom_flat=geom_flat)
+                          skip_sh_grad=dL_drgb_gated_out is not None, geom_flat=geom_flat,
+                          want_camera_grad=want_camera_grad)
     return BackwardOutput(pb.dL_dpositions, pb.dL_drotations, pb.dL_dscales, pb.dL_dopacities,
-                          pb.dL_dsh_coeffs, d_means_2d, geom_flat=geom_flat)
+                          pb.dL_dsh_coeffs, d_means_2d, geom_flat=geom_flat, dL_dviewmat=pb.dL_dviewmat)

@@ -183,6 +183,7 @@ class ProjectionBackwardOutput:
     dL_dscales: torch.Tensor
     dL_dopacities: torch.Tensor
     dL_dsh_coeffs: torch.Tensor
+    dL_dviewmat: Optional[torch.Tensor] = None  # [4,4] camera gradient (project_backward(want_camera_grad=True))
 
 
 @dataclass
@@ -246,3 +247,4 @@ class BackwardOutput:
     dL_dsh_coeffs: torch.Tensor
     dL_dmeans_2d: torch.Tensor
     geom_flat: Optional[torch.Tensor] = None    # [11N] buffer the four geometry gradients are views of (DP exchange)
+    dL_dviewmat: Optional[torch.Tensor] = None  # [4,4] dL/d(world-to-camera matrix), render_backward(want_camera_grad=True)

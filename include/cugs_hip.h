@@ -547,6 +547,48 @@ int cugs_project_backward_adam_mcmc(int64_t n, int num_coeffs, int active_degree
                                     const float* grad_accum, const cugs_adam_fused* adam_host,
                                     const cugs_mcmc_fused* mcmc_host, float* dL_dmeans_2d_out, void* stream);
 
+/* ---- camera pose gradient (not in the reference) ------------------------------------------------
+ * cugs_project_backward_pose / _adam_pose / _adam_mcmc_pose: the entry point of the same name without `_pose`, bit for
+ * bit in every output it has, plus dL/dview, the gradient with respect to cugs_camera.view: t = W p + tvec with
+ * W = view[0..2][0..2], tvec[r] = view[r*4+3].  Per live Gaussian with radii > 0 and an invertible Sigma':
+ * dL/dtvec = dt (the gradient of its camera-space position, depth-map word included) and dL/dW = dt (x) p + J^T K
+ * (K = dL/d(J W)); every other Gaussian adds 0.  The SH view direction is held constant (as dL_dpositions holds it).
+ * dL_dview: device float[16] in the layout of cugs_camera.view, row 3 written 0.  rows: optional device [n,12], each
+ * Gaussian's dL/dW (row-major) then dL/dtvec; NULL in production.  workspace: cugs_pose_grad_workspace_bytes(n)
+ * device bytes, 16-byte aligned.  The workgroup partials are summed in fp64 in a fixed order by two more launches on
+ * `stream` and rounded once: the same bits from run to run, no host sync.  CUGS_EINVAL for a NULL pose_host or
+ * dL_dview, CUGS_EWORKSPACE for a workspace that is too small, before anything is queued; n == 0 writes 16 zeros. */
+typedef struct cugs_pose_grad {
+    float* dL_dview;
+    float* rows;
+    void* workspace;
+    size_t workspace_bytes;
+} cugs_pose_grad;
+size_t cugs_pose_grad_workspace_bytes(int64_t n);
+int cugs_project_backward_pose(int64_t n, int num_coeffs, int active_degree,
+                               const float* positions, const float* rotations, const float* scales,
+                               const float* opacities, const float* sh_coeffs, const int32_t* radii,
+                               const uint8_t* colour_gate, const cugs_camera* camera_host,
+                               float scale_modifier, const float* grad_accum,
+                               const float* dL_dmeans_2d, const float* dL_dcov_2d_inv,
+                               const float* dL_drgb, const float* dL_dopacity_act,
+                               float* dL_dpositions, float* dL_drotations, float* dL_dscales,
+                               float* dL_dopacities, float* dL_dsh_coeffs, float* dL_dmeans_2d_out,
+                               float* dL_drgb_gated_out, const cugs_pose_grad* pose_host, void* stream);
+int cugs_project_backward_adam_pose(int64_t n, int num_coeffs, int active_degree, float* positions,
+                                    float* rotations, float* scales, float* opacities, float* sh_coeffs,
+                                    const int32_t* radii, const uint8_t* colour_gate,
+                                    const cugs_camera* camera_host, float scale_modifier,
+                                    const float* grad_accum, const cugs_adam_fused* adam_host,
+                                    float* dL_dmeans_2d_out, const cugs_pose_grad* pose_host, void* stream);
+int cugs_project_backward_adam_mcmc_pose(int64_t n, int num_coeffs, int active_degree, float* positions,
+                                         float* rotations, float* scales, float* opacities, float* sh_coeffs,
+                                         const int32_t* radii, const uint8_t* colour_gate,
+                                         const cugs_camera* camera_host, float scale_modifier,
+                                         const float* grad_accum, const cugs_adam_fused* adam_host,
+                                         const cugs_mcmc_fused* mcmc_host, float* dL_dmeans_2d_out,
+                                         const cugs_pose_grad* pose_host, void* stream);
+
 /* Device properties the host side needs without linking the HIP runtime itself. */
 int cugs_device_count(int* count_host);
 
