@@ -122,6 +122,40 @@ __device__ __forceinline__ ActiveRect active_rect(unsigned long long active, flo
     return ActiveRect{quad_cx + (float)x0, quad_cy + (float)y0, (float)(x1 - x0), (float)(y1 - y0)};
 }
 
+// ---------------------------------------------------------------------------------------
+// Hit groups.  Both blend kernels take the set bits of a sub-batch's hit mask FOUR at a time: the bits are popped first -
+// scalar work on the wave-uniform ballot - and the four per-pixel steps that follow are straight-line code with ONE
+// "is any pixel of mine still open" vote behind them instead of one per step.  A step taken after the last pixel closed
+// changes nothing: `open == 0` is folded into alpha, so the step's alpha, weight and gates are exactly 0.
+// The backward keeps the four LDS record indices (float4 units, < 768) in the 16-bit fields of one 64-bit scalar.
+// ---------------------------------------------------------------------------------------
+#define CUGS_HIT_GROUP 4
+__device__ __forceinline__ unsigned cugs_pop_hit_desc(unsigned long long& mask) {       // highest set bit; mask != 0
+    const unsigned bit = 63u - (unsigned)__builtin_clzll(mask);
+    mask &= ~(1ull << bit);
+    return bit;
+}
+__device__ __forceinline__ unsigned cugs_pop_hit_asc(unsigned long long& mask) {        // lowest set bit; mask != 0
+    const unsigned bit = (unsigned)__builtin_ctzll(mask);
+    mask &= mask - 1ull;
+    return bit;
+}
+// the four highest bits of `mask` (at least four are set) as record indices rec_base + bit * CUGS_REC_F4, first popped
+// in field 0
+__device__ __forceinline__ unsigned long long cugs_pop_hits4_desc(unsigned long long& mask, unsigned rec_base) {
+    const unsigned r0 = rec_base + cugs_pop_hit_desc(mask) * CUGS_REC_F4;
+    const unsigned r1 = rec_base + cugs_pop_hit_desc(mask) * CUGS_REC_F4;
+    const unsigned r2 = rec_base + cugs_pop_hit_desc(mask) * CUGS_REC_F4;
+    const unsigned r3 = rec_base + cugs_pop_hit_desc(mask) * CUGS_REC_F4;
+    return (unsigned long long)(r0 | (r1 << 16)) | ((unsigned long long)(r2 | (r3 << 16)) << 32);
+}
+__device__ __forceinline__ int cugs_hit(unsigned long long hitrecs, int field) {
+    return (int)((hitrecs >> (16 * field)) & 0xFFFFull);
+}
+__device__ __forceinline__ unsigned long long cugs_set_hit(unsigned long long hitrecs, int field, unsigned rec) {
+    return (hitrecs & ~(0xFFFFull << (16 * field))) | ((unsigned long long)rec << (16 * field));
+}
+
 // forward.cu:124-141 / backward.cu:123-137 for one pixel, written so that every per-lane decision
 // stays in VECTOR registers.  (hipcc keeps a C++ `bool` that differs per lane as a 64-bit lane mask in
 // scalar registers and turns `a && b`, `done |= x` into s_and/s_or_b64; a CU has ONE scalar unit for its

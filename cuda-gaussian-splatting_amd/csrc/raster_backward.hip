@@ -59,6 +59,7 @@ namespace {
 // Against reducing nine values over 64 lanes in every step (38 units) this costs ~19 units per step; the pending
 // Gaussians are flushed before the record batch they point into is re-staged.
 #define CUGS_BWD_HITS 4
+static_assert(CUGS_BWD_HITS == CUGS_HIT_GROUP, "a hit group is one flush");
 #ifndef CUGS_BWD_HSTRIDE
 #define CUGS_BWD_HSTRIDE 64        /* float2 per Gaussian block: the 64 pixels, no padding - see the LDS budget below */
 #endif
@@ -67,7 +68,8 @@ namespace {
 // STATS (dev builds only): step counters written to accumulator row `stats_row` (tools/ablate_backward.py).
 // DEPTH: the depth / alpha maps' gradients too (dL_ddepth_map, dL_dalpha: [H,W], either may be NULL = zero).
 template <bool PACKED, bool WIDE, bool STATS, bool DEPTH = false>
-__global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, RasterSrc src,
+__global__ __launch_bounds__(CUGS_BLOCK) __attribute__((amdgpu_waves_per_eu(DEPTH ? 7 : 8)))
+void k_raster_backward(RasterGeom geo, RasterSrc src,
                                                                 const float* __restrict__ dL_dcolor,
                                                                 const float* __restrict__ final_T,
                                                                 const int32_t* __restrict__ n_contrib,
@@ -152,7 +154,13 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
     float rem = (inside && max_contrib > 0) ? (float)max_contrib : -1.0f;
     float open = (inside && max_contrib > 0) ? 1.0f : 0.0f;
     bool wave_done = (__ballot(open != 0.0f) == 0ull);
-    int pending = 0;                                            // Gaussians waiting in s_contrib (wave-uniform)
+    // The hit loop works in GROUPS of CUGS_BWD_HITS hits: the record indices are popped from the sub-batch's hit mask
+    // first (scalar work, constant shifts), then the four phase-1 steps run as straight-line code with constant
+    // contribution slots, ONE "all my pixels are closed" vote follows, then phase 2.  `pending` counts the hits of an
+    // unfinished group: popped into hitrecs[0 .. pending) at the end of a sub-batch, NOT yet evaluated; the next
+    // sub-batch of the same 256-record batch tops the group up (its cull then sees an `open` that is up to three steps
+    // old - a larger rectangle, so still conservative), the end of the batch runs what is left one step at a time.
+    int pending = 0;                                            // wave-uniform, 0 .. CUGS_BWD_HITS - 1 between groups
     unsigned st_steps = 0, st_contrib = 0, st_lanes = 0, st_batches = 0, st_tested = 0, st_open = 0;   // STATS only
 
     // phase 2 for the `cnt` pending Gaussians of this wave
@@ -196,6 +204,40 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
         }
     };
 
+    // phase 1 for the record at float4 index `rec` (wave-uniform); its contribution goes to slot `slot` of the wave's
+    // block.  Inlined at each call: in the group loop `slot` is a constant and the store takes an immediate offset.
+    auto step = [&](const int rec, const int slot) __attribute__((always_inline)) {
+        if (STATS) ++st_steps;
+        const float4 g0 = s_rec[rec], g1 = s_rec[rec + 1], col = s_rec[rec + 2];
+        const float o = g1.y;
+
+        // ---- decisions (backward.cu:123-145) as 0/1 floats
+        PixelEval e;
+        const float alpha = pixel_alpha_raw(pxf, pyf, g0.x, g0.y, g0.z, g0.w, g1.x, o, open, e);
+        const float passf = passes_alpha_min(alpha);           // alpha >= 1/255 (0 for a finished pixel)
+        rem -= passf;                                          // contributors counted from the END (Q1)
+        open = sat_add(rem, 1.0f);                             // 0 once a passer fell beyond n_contrib
+        const float k = passf * open;                          // 1: this Gaussian contributes here
+        const float al = alpha * k;
+        // clamp gate (backward.cu:181-191): o e >= 0.99 <=> alpha == 0.99f zeroes dL/do and dL/dpower,
+        // dL/drgb still flows
+        const float gk = k * below_alpha_cap(alpha);
+
+        // ---- values (v_rcp_f32 + FMAs); k == 0 makes both outputs exactly zero
+        const float rcp = __builtin_amdgcn_rcpf(1.0f - al);    // al <= 0.99; rcp(1) == 1 exactly
+        T *= rcp;                                              // T_before = T_after / (1 - alpha)
+        const float weight = al * T;
+        float G = fmaf(dC2, col.w, fmaf(dC1, col.z, dC0 * col.x));
+        if (DEPTH) G = fmaf(dDp, col.y, G);                    // + dL/dD z (record word 9)
+        const float gate = fmaf(T, G, -(rcp * D)) * gk;        // dL/dalpha, gated
+        D = fmaf(weight, G, D);
+        if (STATS) {
+            const unsigned long long lm = __ballot(k != 0.0f);
+            if (lm) { ++st_contrib; st_lanes += __popcll(lm); st_open += __popcll(__ballot(open != 0.0f)); }
+        }
+        s_contrib[wave][slot][lane] = make_float2(weight, gate * e.e);
+    };
+
     for (int batch = num_batches - 1; batch >= 0; --batch) {
         // The vote word is the first word of the wave's own contribution block: every pending Gaussian has been flushed
         // when a wave arrives here, nobody else touches the block, all four waves read the words between this barrier
@@ -220,48 +262,35 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_backward(RasterGeom geo, 
                                          ar.wy);
                 unsigned long long mask = __ballot(hit);
                 if (STATS) st_tested += min(CUGS_WAVE, batch_count - sub * CUGS_WAVE);
-                while (mask != 0ull) {                                     // back to front: highest bit first
-                    if (STATS) ++st_steps;
-                    const int bit = 63 - __builtin_clzll(mask);
-                    mask &= ~(1ull << bit);
-                    const int rec = (sub * CUGS_WAVE + bit) * CUGS_REC_F4;
-                    const float4 g0 = s_rec[rec], g1 = s_rec[rec + 1], col = s_rec[rec + 2];
-                    const float o = g1.y;
-
-                    // ---- decisions (backward.cu:123-145) as 0/1 floats
-                    PixelEval e;
-                    const float alpha = pixel_alpha_raw(pxf, pyf, g0.x, g0.y, g0.z, g0.w, g1.x, o, open, e);
-                    const float passf = passes_alpha_min(alpha);           // alpha >= 1/255 (0 for a finished pixel)
-                    rem -= passf;                                          // contributors counted from the END (Q1)
-                    open = sat_add(rem, 1.0f);                             // 0 once a passer fell beyond n_contrib
-                    const float k = passf * open;                          // 1: this Gaussian contributes here
-                    const float al = alpha * k;
-                    // clamp gate (backward.cu:181-191): o e >= 0.99 <=> alpha == 0.99f zeroes dL/do and dL/dpower,
-                    // dL/drgb still flows
-                    const float gk = k * below_alpha_cap(alpha);
-
-                    // ---- values (v_rcp_f32 + FMAs); k == 0 makes both outputs exactly zero
-                    const float rcp = __builtin_amdgcn_rcpf(1.0f - al);    // al <= 0.99; rcp(1) == 1 exactly
-                    T *= rcp;                                              // T_before = T_after / (1 - alpha)
-                    const float weight = al * T;
-                    float G = fmaf(dC2, col.w, fmaf(dC1, col.z, dC0 * col.x));
-                    if (DEPTH) G = fmaf(dDp, col.y, G);                    // + dL/dD z (record word 9)
-                    const float gate = fmaf(T, G, -(rcp * D)) * gk;        // dL/dalpha, gated
-                    D = fmaf(weight, G, D);
-                    if (STATS) {
-                        const unsigned long long lm = __ballot(k != 0.0f);
-                        if (lm) { ++st_contrib; st_lanes += __popcll(lm); st_open += __popcll(__ballot(open != 0.0f)); }
-                    }
-                    s_contrib[wave][pending][lane] = make_float2(weight, gate * e.e);
-                    hitrecs = (hitrecs & ~(0xFFFFull << (16 * pending))) | ((unsigned long long)(unsigned)rec << (16 * pending));
-                    if (++pending == CUGS_BWD_HITS) {
-                        flush(CUGS_BWD_HITS);
+                const unsigned rec_sub = (unsigned)(sub * CUGS_WAVE * CUGS_REC_F4);
+                // ---- whole groups: four hits (back to front: highest bit first), straight-line
+                while (pending + __popcll(mask) >= CUGS_BWD_HITS) {
+                    if (pending == 0) {
+                        hitrecs = cugs_pop_hits4_desc(mask, rec_sub);       // constant shifts
+                    } else {                                               // top up the group a sub-batch left behind
+                        do hitrecs = cugs_set_hit(hitrecs, pending, rec_sub + cugs_pop_hit_desc(mask) * CUGS_REC_F4);
+                        while (++pending < CUGS_BWD_HITS);
                         pending = 0;
                     }
-                    if (__ballot(open != 0.0f) == 0ull) { wave_done = true; break; }
+                    step(cugs_hit(hitrecs, 0), 0);
+                    step(cugs_hit(hitrecs, 1), 1);
+                    step(cugs_hit(hitrecs, 2), 2);
+                    step(cugs_hit(hitrecs, 3), 3);
+                    // ONE vote per group.  A step taken after the last pixel closed has k == 0 in every lane: al = 0,
+                    // rcp(1) = 1, weight = gate = 0 - T, D and rem stay, the sums gain +0.0f.
+                    const bool closed = (__ballot(open != 0.0f) == 0ull);
+                    flush(CUGS_BWD_HITS);
+                    if (closed) { wave_done = true; mask = 0ull; break; }
+                }
+                // ---- fewer than four left: they wait, as record indices, for the next sub-batch of this batch
+                while (mask != 0ull) {
+                    hitrecs = cugs_set_hit(hitrecs, pending, rec_sub + cugs_pop_hit_desc(mask) * CUGS_REC_F4);
+                    ++pending;
                 }
             }
-            if (pending) {                 // before s_rec is re-staged (and at the end of the wave's walk)
+            if (pending) {                 // the partial group: before s_rec is re-staged (and at the end of the wave's walk)
+                for (int p = 0; p < pending; ++p) step(cugs_hit(hitrecs, p), p);
+                if (__ballot(open != 0.0f) == 0ull) wave_done = true;
                 flush(pending);
                 pending = 0;
             }

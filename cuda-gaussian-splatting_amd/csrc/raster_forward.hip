@@ -69,6 +69,26 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
     float open = inside ? 1.0f : 0.0f;                  // 1 while the pixel still blends, 0 once T < 1/255
     bool wave_done = (__ballot(open != 0.0f) == 0ull);
 
+    // one (wave, Gaussian) step; rp: the record in LDS (wave-uniform address: broadcast)
+    auto step = [&](const float4* rp) __attribute__((always_inline)) {
+        const float4 g0 = rp[0], g1 = rp[1], col = rp[2];
+        const float o = g1.y;
+        PixelEval e;
+        // decisions as 0/1 floats (v_fma ... clamp, cugs_raster_common.h): no v_cmp / v_cndmask pairs
+        const float alpha = pixel_alpha_raw(pxf, pyf, g0.x, g0.y, g0.z, g0.w, g1.x, o, open, e);
+        const float passf = passes_alpha_min(alpha);           // alpha >= 1/255 (forward.cu:141)
+        const float al = alpha * passf;
+        // al == 0 (skipped or finished pixel: open is folded into alpha) leaves C, T and count untouched exactly
+        const float weight = al * T;
+        if (DEPTH) C0Z = __builtin_elementwise_fma((v2f){weight, weight}, (v2f){col.x, col.y}, C0Z);
+        else C0 = fmaf(weight, col.x, C0);
+        C12 = __builtin_elementwise_fma((v2f){weight, weight}, (v2f){col.z, col.w}, C12);   // record words 10,11: an aligned pair
+        T *= (1.0f - al);
+        count += passf;
+        open *= passes_alpha_min(T);                            // T < 1/255 -> done (forward.cu:150-156): the same
+                                                                // threshold; only a passing Gaussian can lower T
+    };
+
     for (int batch = 0; batch < num_batches; ++batch) {
         // whole-tile early exit (forward.cu:97-101), one flag per wave instead of an atomicMin
         if (lane == 0) s_wave_done[wave] = wave_done ? 1 : 0;
@@ -88,25 +108,19 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
                     hit = may_touch_quad(s_rec[j * CUGS_REC_F4 + 0], s_rec[j * CUGS_REC_F4 + 1], ar.x0, ar.y0, ar.wx,
                                          ar.wy);
                 unsigned long long mask = __ballot(hit);
-                while (mask != 0ull) {                                      // front to back
-                    const float4* rp = s_rec + (sub * CUGS_WAVE + __builtin_ctzll(mask)) * CUGS_REC_F4;
-                    mask &= mask - 1ull;
-                    const float4 g0 = rp[0], g1 = rp[1], col = rp[2];       // wave-uniform address: broadcast
-                    const float o = g1.y;
-                    PixelEval e;
-                    // decisions as 0/1 floats (v_fma ... clamp, cugs_raster_common.h): no v_cmp / v_cndmask pairs
-                    const float alpha = pixel_alpha_raw(pxf, pyf, g0.x, g0.y, g0.z, g0.w, g1.x, o, open, e);
-                    const float passf = passes_alpha_min(alpha);           // alpha >= 1/255 (forward.cu:141)
-                    const float al = alpha * passf;
-                    // al == 0 (skipped or finished pixel) leaves C, T and count untouched exactly
-                    const float weight = al * T;
-                    if (DEPTH) C0Z = __builtin_elementwise_fma((v2f){weight, weight}, (v2f){col.x, col.y}, C0Z);
-                    else C0 = fmaf(weight, col.x, C0);
-                    C12 = __builtin_elementwise_fma((v2f){weight, weight}, (v2f){col.z, col.w}, C12);   // record words 10,11: an aligned pair
-                    T *= (1.0f - al);
-                    count += passf;
-                    open *= passes_alpha_min(T);                            // T < 1/255 -> done (forward.cu:150-156): the same
-                                                                            // threshold; only a passing Gaussian can lower T
+                const float4* sub_rec = s_rec + sub * CUGS_WAVE * CUGS_REC_F4;
+                // whole groups, front to back: four bits popped, four straight-line steps, ONE vote.  The steps a
+                // finished wave still takes have open == 0 in every lane and change nothing (see `step`).
+                while (__popcll(mask) >= CUGS_HIT_GROUP) {
+                    const float4* r0 = sub_rec + cugs_pop_hit_asc(mask) * CUGS_REC_F4;
+                    const float4* r1 = sub_rec + cugs_pop_hit_asc(mask) * CUGS_REC_F4;
+                    const float4* r2 = sub_rec + cugs_pop_hit_asc(mask) * CUGS_REC_F4;
+                    const float4* r3 = sub_rec + cugs_pop_hit_asc(mask) * CUGS_REC_F4;
+                    step(r0); step(r1); step(r2); step(r3);
+                    if (__ballot(open != 0.0f) == 0ull) { wave_done = true; mask = 0ull; break; }
+                }
+                while (mask != 0ull) {                                      // the sub-batch's last one to three hits
+                    step(sub_rec + cugs_pop_hit_asc(mask) * CUGS_REC_F4);
                     if (__ballot(open != 0.0f) == 0ull) { wave_done = true; break; }
                 }
             }
