@@ -185,12 +185,12 @@ __device__ __forceinline__ TileRect tile_rect_of(float x, float y, int radius, i
     return r;
 }
 
-// The sort's per-Gaussian record (sort.hip): the depth key and the 16-byte tile rectangle {x0, y0, w | h << 16,
+// The sort's per-Gaussian record (sort_emit.h): the depth key and the 16-byte tile rectangle {x0, y0, w | h << 16,
 // tiles_touched}.  One definition for the two producers - k_depth_keys_rect, which reads the projection's outputs back
 // (the stage boundary of sort_gaussians, sorting.cu:115), and k_project_forward, which has them in registers
 // (cugs_project_forward_keyed: render() saves a launch and 40 MB) - so the two routes cannot differ.
 // `tr` is only read when tiles > 0 && radius > 0.  three_pass: the key is the depth's offset from the near plane
-// (sort.hip, RADIX_DEPTH); *out_of_range reports a Gaussian that emits pairs outside that route's range.
+// (sort_workspace.h, RADIX_DEPTH); *out_of_range reports a Gaussian that emits pairs outside that route's range.
 constexpr int CUGS_DEPTH_BITS = 9;
 constexpr uint32_t CUGS_DEPTH_KEY_BASE = 0x3E4CCCCCu;  // float bits of 0.2f, minus one: offsets of visible splats start at 1, 0 = "sorts first"
 constexpr uint32_t CUGS_DEPTH_KEY_SPAN = 1u << (3 * CUGS_DEPTH_BITS);

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_forward(int64_t n, int d
     p.tiles_touched[idx] = tiles;
     p.opacities_act[idx] = opa;
     if (p.sort_keys) {                                                 // kernel-uniform
-        // what k_depth_keys_rect (sort.hip) would make of the four stores above, while they are still in registers
+        // what k_depth_keys_rect (sort_emit.h) would make of the four stores above, while they are still in registers
         bool bad;
         const SortRecord rec = sort_record_of(depth, tiles, radius, tr, true, &bad);
         if (bad) atomicOr(p.sort_range_flag, 1u);

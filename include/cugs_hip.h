@@ -168,7 +168,7 @@ int cugs_sort_pairs_predicted(int64_t n, int64_t capacity, const float* means_2d
  * skipped (one kernel and 40 MB per million Gaussians).  Outputs and validity rule are those of
  * cugs_sort_pairs_predicted.  BOTH fallbacks (a count above the capacity, or -1) are cugs_sort_count_pairs followed by
  * cugs_sort_pairs, which rebuild everything from the arrays: on images of up to 10 240 tiles and up to 2 M Gaussians this
- * entry point bins the pairs straight into their tiles' lists (no pair-level radix passes, csrc/sort.hip k_bin_*) and
+ * entry point bins the pairs straight into their tiles' lists (no pair-level radix passes, csrc/sort_bin.h k_bin_*) and
  * does not leave in `workspace` what cugs_sort_pairs alone continues from.  On either miss every tile range is {0,0}:
  * a blend queued behind the sort before the host has looked at the count then does nothing (the index buffer is
  * unwritten).  pair_workspace is not touched on that route (it may still be sized as for cugs_sort_pairs_predicted). */

@@ -86,7 +86,7 @@ def test_sort_parity_bit_exact(pkg, orc, dev, n, w, h, mu_s):
 
 @pytest.mark.parametrize("n,expect", [(230_000, "16"), (300_000, "64"), (600_000, "64")])
 def test_render_sort_routes_by_size(pkg, orc, dev, n, expect):
-    """render()'s sort at the sizes where its radix passes change shape (sort.hip: scan_free / sup_block): a pair level of
+    """render()'s sort at the sizes where its radix passes change shape (sort_workspace.h: scan_free / sup_block): a pair level of
     ~470 workgroups (super-blocks of 16), of ~610 and ~1230 (super-blocks of 64); each with the packed rectangles riding
     through the depth passes (n <= 1 M, 120 x 68 tiles).  (Pair levels beyond 4096 workgroups - the classic three kernels
     per pass - are the dense full-size view and config 4.)  Pairs, order, ranges and the image against the
@@ -111,7 +111,7 @@ def test_render_sort_routes_by_size(pkg, orc, dev, n, expect):
 def test_sort_both_pair_routes(pkg, orc, dev, mu_s, dense):
     """The pair-level sort has two routes to the same permutation: pairs emitted in depth order + two radix passes
     by tile id (sparse views), or pairs emitted in tile-column order + one pass by tile row (>= 13 pairs per
-    Gaussian, sort.hip column_path_pays).  The same 1080p scene at two splat scales takes one each - exact and
+    Gaussian, sort_workspace.h column_path_pays).  The same 1080p scene at two splat scales takes one each - exact and
     predicted-capacity entry points - and both must give the oracle's keys, order and tile ranges."""
     n, w, h = 50000, 1920, 1080
     arrays, cam = _scene(pkg, n, w, h, 0, seed=17, mu_s=mu_s)

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _bucket(length):
-    """order_bucket of csrc/sort.hip: 32 x 16 length classes (4 bits below the leading one), empty tiles last."""
+    """order_bucket of csrc/sort_tile_order.h: 32 x 16 length classes (4 bits below the leading one), empty tiles last."""
     if length == 0:
         return 512
     e = int(length).bit_length() - 1

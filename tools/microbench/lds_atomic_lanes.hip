@@ -1,5 +1,5 @@
 // lds_atomic_lanes.hip — what does an LDS atomic instruction cost on gfx950 when few of its lanes are active, and what do
-// scattered 4-byte global stores cost per active lane?  (dev tool, not product; the numbers behind csrc/sort.hip's
+// scattered 4-byte global stores cost per active lane?  (dev tool, not product; the numbers behind csrc/sort_bin.h's
 // k_bin_count - four atomics per Gaussian through a grid of differences instead of one per covered tile from divergent
 // loops - and behind the store cost of k_bin_scatter.)
 // Build: hipcc --offload-arch=gfx950 -O3 -o lds_atomic_lanes.bin lds_atomic_lanes.hip ; run on the GPU box.
