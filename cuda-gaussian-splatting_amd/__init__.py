@@ -20,6 +20,7 @@ from .fused_adam import (AdamConfig, FusedAdam, ParamGroup, PositionLRConfig,  #
 from .loss import combined_loss, combined_loss_and_grad, l1_loss, ssim, ssim_loss  # noqa: F401
 from .densification import DensificationConfig, DensificationController, DensificationStats  # noqa: F401
 from .mcmc import MCMCConfig, MCMCController, MCMCStats  # noqa: F401
+from .gaussian_init import init_gaussians_from_sparse, knn_mean_distances  # noqa: F401
 from .pose import apply_se3, se3_exp, viewmat_grad_to_se3  # noqa: F401
 from . import pose  # noqa: F401
 from .ply_io import read_gaussian_ply, restore_optimizer, write_gaussian_ply  # noqa: F401

@@ -52,6 +52,7 @@ class McmcFused(C.Structure):
                 ("noise", C.c_void_p)]
 
 
+KNN_AUTO, KNN_EXHAUSTIVE, KNN_TREE = 0, 1, 2                            # CUGS_KNN_*
 MCMC_STREAM_NOISE, MCMC_STREAM_JITTER, MCMC_STREAM_SAMPLE = 0, 1, 2     # CUGS_MCMC_STREAM_*
 
 
@@ -147,6 +148,9 @@ SIGNATURES = {
     "cugs_ply_pack": (_I, [_L, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     "cugs_ply_unpack": (_I, [_L, _I, _I, _P, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),
     "cugs_image_to_float": (_I, [_I, _I, _P, _I, _I, _P, _P]),
+    "cugs_knn_workspace_bytes": (C.c_size_t, [_L, _I]),
+    "cugs_knn_mean_distances": (_I, [_L, _I, _P, _P, _P, C.c_size_t, _I, _P]),
+    "cugs_init_from_points": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cugs_device_count": (_I, [C.POINTER(C.c_int)]),
 }
 

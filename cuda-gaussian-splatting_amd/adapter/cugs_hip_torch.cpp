@@ -1088,4 +1088,59 @@ cugs_mcmc_fused MCMCController::fused_args(int step, const torch::Tensor& noise)
     return a;
 }
 
+// ---- core/gaussian_init.cpp over csrc/knn.hip ----
+namespace {
+torch::Device init_device(const torch::Tensor& positions, const c10::optional<torch::Device>& device) {
+    if (device.has_value()) {
+        if (device->is_cuda() && !device->has_index()) return torch::Device(torch::kCUDA, c10::hip::current_device());
+        return *device;
+    }
+    if (positions.is_cuda()) return positions.device();
+    return torch::Device(torch::kCUDA, c10::hip::current_device());
+}
+torch::Tensor mean_distances_on(const torch::Tensor& pos, int k_neighbors, int route) {
+    TORCH_CHECK(k_neighbors >= 1 && k_neighbors <= 16, "k_neighbors must be 1..16, got ", k_neighbors);
+    TORCH_CHECK(route == CUGS_KNN_AUTO || route == CUGS_KNN_EXHAUSTIVE || route == CUGS_KNN_TREE, "unknown route ", route);
+    const int64_t n = pos.size(0);
+    auto out = torch::empty({n}, fopt(pos));
+    if (n == 0) return out;
+    torch::Tensor ws;
+    if (route != CUGS_KNN_EXHAUSTIVE) ws = workspace(pos.device(), cugs_knn_workspace_bytes(n, k_neighbors), 7);
+    check(cugs_knn_mean_distances(n, k_neighbors, ptr<float>(pos), ptr<float>(out), ws.defined() ? ws.data_ptr() : nullptr,
+                                  ws.defined() ? static_cast<size_t>(ws.numel()) : 0, route, stream_of(pos)),
+          "cugs_knn_mean_distances");
+    return out;
+}
+torch::Tensor positions_on(const torch::Tensor& positions, const torch::Device& dev) {
+    TORCH_CHECK(positions.dim() == 2 && positions.size(1) == 3, "positions must be [N, 3]");
+    return positions.to(dev, torch::kFloat32).contiguous();
+}
+}  // namespace
+
+torch::Tensor knn_mean_distances(const torch::Tensor& positions, int k_neighbors, int route,
+                                 c10::optional<torch::Device> device) {
+    return mean_distances_on(positions_on(positions, init_device(positions, device)), k_neighbors, route);
+}
+
+ModelTensors init_gaussians_from_sparse(const torch::Tensor& positions, const torch::Tensor& colors, int sh_degree,
+                                        int k_neighbors, int route, c10::optional<torch::Device> device) {
+    TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "SH degree must be 0..", 3, ", got ", sh_degree);   // gaussian_init.cpp:77-78
+    const auto dev = init_device(positions, device);
+    auto pos = positions_on(positions, dev);
+    const int64_t n = pos.size(0);
+    TORCH_CHECK(colors.dim() == 2 && colors.size(0) == n && colors.size(1) == 3, "colors must be [N, 3]");
+    TORCH_CHECK(colors.scalar_type() == torch::kUInt8, "colors must be uint8");
+    auto col = colors.to(dev).contiguous();
+    const int64_t C = static_cast<int64_t>(sh_degree + 1) * (sh_degree + 1);
+    ModelTensors m{torch::empty({n, 3}, fopt(pos)), torch::empty({n, 3, C}, fopt(pos)), torch::empty({n, 1}, fopt(pos)),
+                   torch::empty({n, 4}, fopt(pos)), torch::empty({n, 3}, fopt(pos))};
+    if (n == 0) return m;                                                                            // :88-95
+    auto mean = mean_distances_on(pos, k_neighbors, route);
+    check(cugs_init_from_points(n, static_cast<int>(C), ptr<float>(pos), col.data_ptr<uint8_t>(), ptr<float>(mean),
+                                ptr<float>(m.positions), ptr<float>(m.sh_coeffs), ptr<float>(m.opacities),
+                                ptr<float>(m.rotations), ptr<float>(m.scales), stream_of(pos)),
+          "cugs_init_from_points");
+    return m;
+}
+
 }  // namespace cugs_hip

@@ -236,4 +236,15 @@ bool write_gaussian_ply(const std::string& path, const ModelTensors& model, cons
 ModelTensors read_gaussian_ply(const std::string& path, const torch::Device& device = torch::kCPU,
                                FusedAdam* optimizer = nullptr);
 
+// core/gaussian_init.hpp over csrc/knn.hip: a model from a point cloud, on the device.
+// positions [n, 3] float32, colors [n, 3] uint8, on any device (moved to `device`, which must be a HIP device; the
+// default takes the positions' device, or the current HIP device if they are on the CPU).  Rows keep the input order.
+// knn_mean_distances: compute_knn_mean_distances (gaussian_init.cpp:25-68), exact; k is clamped to n - 1.
+// `route`: CUGS_KNN_AUTO / CUGS_KNN_EXHAUSTIVE / CUGS_KNN_TREE - the same bits on each.
+torch::Tensor knn_mean_distances(const torch::Tensor& positions, int k_neighbors = 3, int route = CUGS_KNN_AUTO,
+                                 c10::optional<torch::Device> device = c10::nullopt);
+ModelTensors init_gaussians_from_sparse(const torch::Tensor& positions, const torch::Tensor& colors, int sh_degree = 3,
+                                        int k_neighbors = 3, int route = CUGS_KNN_AUTO,
+                                        c10::optional<torch::Device> device = c10::nullopt);
+
 }  // namespace cugs_hip

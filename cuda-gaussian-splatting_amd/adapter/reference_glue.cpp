@@ -11,6 +11,7 @@
 // this file's object); built for real only in the maintainer's tree.
 #include "reference_glue.hpp"
 
+#include "core/gaussian_init.hpp"
 #include "core/sh.hpp"
 #include "core/sh_backward.hpp"
 
@@ -126,5 +127,23 @@ static_assert(std::is_same_v<decltype(&evaluate_sh_cuda),
                              torch::Tensor (*)(int, const torch::Tensor&, const torch::Tensor&)>);
 static_assert(std::is_same_v<decltype(&evaluate_sh_backward_cuda),
                              torch::Tensor (*)(int, const torch::Tensor&, const torch::Tensor&, const torch::Tensor&)>);
+
+// ---- core/gaussian_init.hpp:  the point cloud goes to the device once, the model comes back on the device ----
+GaussianModel init_gaussians_from_sparse(std::span<const SparsePoint> points, int sh_degree, int k_neighbors) {
+    const int64_t n = static_cast<int64_t>(points.size());
+    auto pos = torch::empty({n, 3}, torch::kFloat32);
+    auto col = torch::empty({n, 3}, torch::kUInt8);
+    float* p = n ? pos.data_ptr<float>() : nullptr;
+    uint8_t* c = n ? col.data_ptr<uint8_t>() : nullptr;
+    for (int64_t i = 0; i < n; ++i) {
+        p[3 * i] = points[i].position.x(); p[3 * i + 1] = points[i].position.y(); p[3 * i + 2] = points[i].position.z();
+        c[3 * i] = points[i].color[0]; c[3 * i + 1] = points[i].color[1]; c[3 * i + 2] = points[i].color[2];
+    }
+    auto m = cugs_hip::init_gaussians_from_sparse(pos, col, sh_degree, k_neighbors);
+    GaussianModel model;
+    model.positions = m.positions; model.sh_coeffs = m.sh_coeffs; model.opacities = m.opacities;
+    model.rotations = m.rotations; model.scales = m.scales;
+    return model;
+}
 
 }  // namespace cugs

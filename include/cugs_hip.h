@@ -589,6 +589,36 @@ int cugs_project_backward_adam_mcmc_pose(int64_t n, int num_coeffs, int active_d
                                          const cugs_mcmc_fused* mcmc_host, float* dL_dmeans_2d_out,
                                          const cugs_pose_grad* pose_host, void* stream);
 
+/* ---- init_gaussians_from_sparse (core/gaussian_init.cpp:25-152) on the device ----------------------------------
+ * The reference turns a point cloud into a model on the CPU: positions copied, the DC coefficient from the colour
+ * (:111-119), opacity logit of 0.1 (:125-126), identity rotations (:129-130) and isotropic scales log(max(m, 1e-7))
+ * (:132-144), m_i = mean distance from point i to its k nearest OTHER points, by a brute-force search on one thread
+ * (compute_knn_mean_distances, :25-68).  Here the search is exact on the device:
+ *   d^2 = (dx*dx + dy*dy) + dz*dz, dx = p_j.x - p_i.x, one fp32 rounding per operation (:48-51); the point itself is
+ *   excluded by index, so a duplicate is a neighbour at distance 0 (:54); k is clamped to n - 1 (:36);
+ *   m_i = (sum of sqrt(d^2) over the k smallest d^2, added in ASCENDING order) / float(k) (:59-64, whose order
+ *   nth_element leaves open); n == 1: m = 1 (:29-33).
+ * cugs_knn_mean_distances writes mean_dist [n] in the input order of the points.  `route`:
+ *   CUGS_KNN_EXHAUSTIVE  every query against every point; needs no workspace (NULL, 0 allowed);
+ *   CUGS_KNN_TREE        Morton order, buckets of 32, a tree of boxes walked per query; same bits as the exhaustive route;
+ *   CUGS_KNN_AUTO        exhaustive for small clouds, the tree from the size DESIGN.md 4.15 records.
+ * TREE and AUTO need cugs_knn_workspace_bytes(n, k) bytes of scratch (monotone in n; 0 for invalid arguments).
+ * k in 1..16, 0 <= n <= 2^30, non-null positions / mean_dist when n > 0, a known route: CUGS_EINVAL otherwise;
+ * CUGS_EWORKSPACE for a short workspace, before anything is queued; n == 0 queues nothing.  Stream-ordered, no host
+ * read-back, nothing allocated, no float atomics: the same bits from run to run.
+ * cugs_init_from_points: one launch that writes the five model arrays (positions [n,3], sh_coeffs [n,3,num_coeffs],
+ * opacities [n,1], rotations [n,4], scales [n,3]) from positions [n,3], colors [n,3] uint8 and mean_dist [n];
+ * num_coeffs in {1, 4, 9, 16}. */
+#define CUGS_KNN_AUTO 0
+#define CUGS_KNN_EXHAUSTIVE 1
+#define CUGS_KNN_TREE 2
+size_t cugs_knn_workspace_bytes(int64_t n, int k);
+int cugs_knn_mean_distances(int64_t n, int k, const float* positions, float* mean_dist, void* workspace,
+                            size_t workspace_bytes, int route, void* stream);
+int cugs_init_from_points(int64_t n, int num_coeffs, const float* positions, const uint8_t* colors,
+                          const float* mean_dist, float* out_positions, float* out_sh, float* out_opacities,
+                          float* out_rotations, float* out_scales, void* stream);
+
 /* Device properties the host side needs without linking the HIP runtime itself. */
 int cugs_device_count(int* count_host);
 
