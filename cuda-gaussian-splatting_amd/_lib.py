@@ -104,6 +104,8 @@ SIGNATURES = {
                                           _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_rasterize_backward_depth": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                            _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "cugs_rasterize_backward_abs": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
+                                         _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cugs_rasterize_forward": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P]),
     "cugs_rasterize_forward_zero": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
@@ -124,6 +126,7 @@ SIGNATURES = {
     "cugs_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_combined_loss": (_I, [_I, _I, _P, _P, _F, _I, _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_densify_accumulate": (_I, [_L, _P, _P, _P, _P, _P, _P]),
+    "cugs_densify_accumulate_strided": (_I, [_L, _P, _L, _P, _P, _P, _P, _P]),
     "cugs_densify_classify": (_I, [_L, _P, _P, _P, _P, _P, _F, _F, _F, _I, _F, _F, _P, _P, _P]),
     "cugs_densify_workspace_bytes": (C.c_size_t, [_L]),
     "cugs_densify_plan": (_I, [_L, _P, _P, C.c_size_t, C.POINTER(C.c_int64), _P]),

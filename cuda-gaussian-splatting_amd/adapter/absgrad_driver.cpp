@@ -1,0 +1,71 @@
+// absgrad_driver: the absolute 2-D mean gradients (AbsGrad) through the C++ host, for
+// tests/test_gpu_absgrad_cpp.py.
+//   absgrad_driver.bin <dir>
+// reads <dir>/{positions,sh,opacities,rotations,scales,dl_dcolor,camera}.f32 (raw float32; the camera file holds the
+// cugs_camera words: view[16] fx fy cx cy width height cam_center[3]), renders, runs render_backward with
+// want_abs_grad = true, feeds the result to DensificationController::accumulate_gradients as it is, and writes
+// <dir>/{d_means_abs,densify_accum,d_positions,d_rotations,d_scales,d_opacities,d_sh}.f32.
+#include "cugs_hip_torch.hpp"
+
+#include <cstdio>
+#include <fstream>
+#include <string>
+#include <vector>
+
+static std::vector<float> read_f32(const std::string& path) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
+    const std::streamsize bytes = f.tellg();
+    f.seekg(0);
+    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
+    f.read(reinterpret_cast<char*>(v.data()), bytes);
+    return v;
+}
+
+static void write_f32(const std::string& path, const torch::Tensor& t) {
+    auto c = t.detach().to(torch::kCPU).contiguous().to(torch::kFloat32);
+    std::ofstream f(path, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(c.data_ptr<float>()), c.numel() * sizeof(float));
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
+    const std::string dir = argv[1];
+    const auto dev = torch::Device(torch::kCUDA, 0);
+    auto load = [&](const char* name, std::vector<int64_t> shape) {
+        auto v = read_f32(dir + "/" + name + ".f32");
+        return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+    };
+    const auto cam_words = read_f32(dir + "/camera.f32");
+    cugs_camera cam{};
+    for (int i = 0; i < 16; ++i) cam.view[i] = cam_words[i];
+    cam.fx = cam_words[16]; cam.fy = cam_words[17]; cam.cx = cam_words[18]; cam.cy = cam_words[19];
+    cam.width = static_cast<int>(cam_words[20]); cam.height = static_cast<int>(cam_words[21]);
+    for (int i = 0; i < 3; ++i) cam.cam_center[i] = cam_words[22 + i];
+    const int64_t n = static_cast<int64_t>(read_f32(dir + "/opacities.f32").size());
+    const int64_t c = static_cast<int64_t>(read_f32(dir + "/sh.f32").size()) / (3 * n);
+    const int w = cam.width, h = cam.height;
+    cugs_hip::ModelTensors model{load("positions", {n, 3}), load("sh", {n, 3, c}), load("opacities", {n, 1}),
+                                 load("rotations", {n, 4}), load("scales", {n, 3})};
+    cugs_hip::RenderSettings settings;
+    settings.active_sh_degree = 3;
+    auto out = cugs_hip::render(model, cam, settings);
+    auto grads = cugs_hip::render_backward(load("dl_dcolor", {h, w, 3}), out, model, cam, settings, nullptr, nullptr, 0, {},
+                                           {}, /*want_camera_grad=*/false, /*want_abs_grad=*/true);
+    if (!grads.dL_dmeans_2d_abs.defined() || grads.dL_dmeans_2d_abs.stride(0) != CUGS_GRAD_STRIDE) {
+        std::fprintf(stderr, "dL_dmeans_2d_abs is not a view of the accumulator rows\n");
+        return 1;
+    }
+    cugs_hip::DensificationController ctl(cugs_hip::DensificationConfig{}, 5.0f);
+    ctl.accumulate_gradients(grads.dL_dmeans_2d_abs, out.radii);          // the strided view, read in place
+    torch::cuda::synchronize();
+    write_f32(dir + "/d_means_abs.f32", grads.dL_dmeans_2d_abs);
+    write_f32(dir + "/densify_accum.f32", ctl.grad_accum());
+    write_f32(dir + "/d_positions.f32", grads.dL_dpositions);
+    write_f32(dir + "/d_rotations.f32", grads.dL_drotations);
+    write_f32(dir + "/d_scales.f32", grads.dL_dscales);
+    write_f32(dir + "/d_opacities.f32", grads.dL_dopacities);
+    write_f32(dir + "/d_sh.f32", grads.dL_dsh_coeffs);
+    std::printf("absgrad_driver ok: n %lld, %dx%d\n", static_cast<long long>(n), w, h);
+    return 0;
+}

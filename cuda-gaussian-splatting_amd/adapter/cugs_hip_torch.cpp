@@ -241,7 +241,7 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
                                            const float background[3], int n_gaussians, const torch::Tensor& packed,
                                            bool unpack, const torch::Tensor& zeroed_accum, const torch::Tensor& tile_order,
                                            const torch::Tensor& depths, const torch::Tensor& dL_ddepth_map,
-                                           const torch::Tensor& dL_dalpha) {
+                                           const torch::Tensor& dL_dalpha, bool want_abs_grad) {
     TORCH_CHECK(dL_dcolor.is_cuda(), "dL_dcolor must be on CUDA");
     const int64_t n = n_gaussians;
     RasterizeBackwardOutput o;
@@ -267,6 +267,8 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
         o.dL_dcov_2d_inv = torch::empty({n, 3}, fopt(dL_dcolor));
         if (depth_route) o.dL_ddepths = torch::empty({n}, fopt(dL_dcolor));
     }
+    if (want_abs_grad)
+        o.dL_dmeans_2d_abs = unpack ? torch::empty({n, 2}, fopt(dL_dcolor)) : o.grad_accum.slice(1, 10, 12);
     if (n == 0) return o;
     auto g = dL_dcolor.contiguous(), m = means_2d.contiguous(), c = cov_2d_inv.contiguous(), r = rgb.contiguous();
     auto op = opacities.contiguous(), tr = tile_ranges.contiguous(), gi = gaussian_indices.contiguous();
@@ -274,6 +276,21 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
     if (tile_order.defined())
         TORCH_CHECK(tile_order.is_contiguous() && tile_order.scalar_type() == torch::kInt32 &&
                     tile_order.numel() == 4 * tr.size(0), "tile_order must be a contiguous [tiles, 4] int32 tensor");
+    if (want_abs_grad) {
+        auto f32 = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
+        auto z = f32(depths), dd = f32(dL_ddepth_map), da = f32(dL_dalpha);
+        check(cugs_rasterize_backward_abs(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
+                                          ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g),
+                                          ptr<float>(ft), ptr<int32_t>(nc), n, ptr<float>(o.grad_accum),
+                                          ptr<float>(o.dL_drgb), ptr<float>(o.dL_dopacity_act), ptr<float>(o.dL_dmeans_2d),
+                                          ptr<float>(o.dL_dcov_2d_inv), prezeroed ? 1 : 0,
+                                          tile_order.defined() ? reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>())
+                                                               : nullptr,
+                                          ptr<float>(z), ptr<float>(dd), ptr<float>(da), ptr<float>(o.dL_ddepths),
+                                          unpack ? ptr<float>(o.dL_dmeans_2d_abs) : nullptr, stream_of(dL_dcolor)),
+              "cugs_rasterize_backward_abs");
+        return o;
+    }
     if (depth_route) {
         auto z = depths.contiguous().to(torch::kFloat32);
         auto f32 = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
@@ -528,7 +545,7 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& ro, const ModelTensors& model,
                                const cugs_camera& camera, const RenderSettings& settings, FusedAdam* fused,
                                const MCMCController* mcmc, int step, const torch::Tensor& dL_ddepth_map,
-                               const torch::Tensor& dL_dalpha, bool want_camera_grad) {
+                               const torch::Tensor& dL_dalpha, bool want_camera_grad, bool want_abs_grad) {
     TORCH_CHECK(!mcmc || fused, "the fused MCMC route needs the FusedAdam (otherwise: compute_regularization, step, "
                 "inject_noise)");
     TORCH_CHECK(dL_dcolor.is_cuda(), "dL_dcolor must be on CUDA device");                             // rasterizer.cpp:122-124
@@ -543,6 +560,7 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
         o.dL_dscales = torch::zeros({0, 3}, fopt(dL_dcolor)); o.dL_dopacities = torch::zeros({0, 1}, fopt(dL_dcolor));
         o.dL_dsh_coeffs = torch::zeros_like(model.sh_coeffs); o.dL_dmeans_2d = torch::zeros({0, 2}, fopt(dL_dcolor));
         if (want_camera_grad) o.dL_dviewmat = torch::zeros({4, 4}, fopt(dL_dcolor));
+        if (want_abs_grad) o.dL_dmeans_2d_abs = torch::zeros({0, 2}, fopt(dL_dcolor));
         return o;
     }
     const int degree = std::min(settings.active_sh_degree, max_sh_degree(model.sh_coeffs));
@@ -564,7 +582,8 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
     auto rb = rasterize_backward(dL_dcolor, ro.means_2d, ro.cov_2d_inv, ro.rgb, ro.opacities_act, ro.tile_ranges,
                                  ro.gaussian_indices, ro.final_T, ro.n_contrib, camera.width, camera.height,
                                  settings.background, static_cast<int>(n), packed, /*unpack=*/false, zeroed, ro.tile_order,
-                                 depth_grads ? ro.depths : torch::Tensor(), dL_ddepth_map, dL_dalpha);
+                                 depth_grads ? ro.depths : torch::Tensor(), dL_ddepth_map, dL_dalpha, want_abs_grad);
+    o.dL_dmeans_2d_abs = rb.dL_dmeans_2d_abs;                   // a view of the rows (undefined without the flag)
     o.dL_dmeans_2d = torch::empty({n, 2}, fopt(dL_dcolor));
     // the camera gradient: its output and the reduction's workspace, both stream-ordered allocations
     cugs_pose_grad pose{};
@@ -747,8 +766,17 @@ void DensificationController::accumulate_gradients(const torch::Tensor& dL_dmean
     const int64_t n = dL_dmeans_2d.size(0);
     TORCH_CHECK(radii.numel() == n, "radii must be [N]");
     if (!grad_accum_.defined() || grad_accum_.size(0) != n) reset_accumulators(n, dL_dmeans_2d.device());
-    auto g = dL_dmeans_2d.contiguous().to(torch::kFloat32);
     auto r = radii.contiguous().to(torch::kInt32);
+    // a strided [N,2] view (BackwardOutput::dL_dmeans_2d_abs: words 10, 11 of the accumulator rows) is read in place
+    const int64_t row = n > 0 ? dL_dmeans_2d.stride(0) : 2;
+    if (dL_dmeans_2d.scalar_type() == torch::kFloat32 && !dL_dmeans_2d.is_contiguous() && dL_dmeans_2d.stride(1) == 1 &&
+        row >= 2 && row % 2 == 0 && reinterpret_cast<uintptr_t>(dL_dmeans_2d.data_ptr()) % 8 == 0) {
+        check(cugs_densify_accumulate_strided(n, dL_dmeans_2d.data_ptr<float>(), row, ptr<int32_t>(r),
+                                              ptr<float>(grad_accum_), ptr<float>(grad_count_), ptr<float>(max_radii_2d_),
+                                              stream_of(dL_dmeans_2d)), "cugs_densify_accumulate_strided");
+        return;
+    }
+    auto g = dL_dmeans_2d.contiguous().to(torch::kFloat32);
     check(cugs_densify_accumulate(n, ptr<float>(g), ptr<int32_t>(r), ptr<float>(grad_accum_), ptr<float>(grad_count_),
                                   ptr<float>(max_radii_2d_), stream_of(g)), "cugs_densify_accumulate");
 }

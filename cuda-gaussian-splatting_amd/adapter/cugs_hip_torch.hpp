@@ -38,6 +38,7 @@ struct RasterizeBackwardOutput {
     torch::Tensor dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv;
     torch::Tensor grad_accum;      // [N,16] packed rows (not in the reference)
     torch::Tensor dL_ddepths;      // [N] dL/dz of the depth map (rasterize_backward(..., depths, ...), unpacked)
+    torch::Tensor dL_dmeans_2d_abs;   // [N,2] AbsGrad sums (want_abs_grad): own tensor unpacked, else grad_accum[:, 10:12]
 };
 struct ProjectionBackwardOutput { torch::Tensor dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs; };
 
@@ -63,9 +64,13 @@ struct RenderOutput {              // rasterizer/rasterizer.hpp:27-46
 };
 // dL_dviewmat (not in the reference): [4,4] dL/d(world-to-camera matrix), render_backward(...,
 // want_camera_grad = true) only, undefined otherwise.
+// dL_dmeans_2d_abs (not in the reference): [N,2] absolute 2-D mean gradients (AbsGrad),
+// render_backward(..., want_abs_grad = true) only, undefined otherwise: a view of words 10, 11 of the blend's accumulator
+// rows (row stride 16, no copy), which it keeps alive; DensificationController::accumulate_gradients reads it in place.
 struct BackwardOutput {
     torch::Tensor dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs, dL_dmeans_2d;
     torch::Tensor dL_dviewmat;
+    torch::Tensor dL_dmeans_2d_abs;
 };
 
 ProjectionOutput project_gaussians(const torch::Tensor& positions, const torch::Tensor& rotations,
@@ -91,7 +96,7 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
                                            const torch::Tensor& packed = {}, bool unpack = true,
                                            const torch::Tensor& zeroed_accum = {}, const torch::Tensor& tile_order = {},
                                            const torch::Tensor& depths = {}, const torch::Tensor& dL_ddepth_map = {},
-                                           const torch::Tensor& dL_dalpha = {});
+                                           const torch::Tensor& dL_dalpha = {}, bool want_abs_grad = false);
 ProjectionBackwardOutput project_backward(const torch::Tensor& dL_dmeans_2d, const torch::Tensor& dL_dcov_2d_inv,
                                           const torch::Tensor& dL_drgb, const torch::Tensor& dL_dopacity_act,
                                           const torch::Tensor& positions, const torch::Tensor& rotations,
@@ -117,7 +122,7 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                                const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
                                FusedAdam* fused = nullptr, const MCMCController* mcmc = nullptr, int step = 0,
                                const torch::Tensor& dL_ddepth_map = {}, const torch::Tensor& dL_dalpha = {},
-                               bool want_camera_grad = false);
+                               bool want_camera_grad = false, bool want_abs_grad = false);
 // `mcmc` (with `fused` only): the regulariser gradient and the position noise of iteration `step` ride in
 // the same launch (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + compute_regularization's
 // gradients, apply_gradients, step, inject_noise(model, step).
@@ -126,6 +131,9 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
 // `want_camera_grad` (not in the reference): BackwardOutput::dL_dviewmat, the gradient with respect to
 // camera.view (row 3 zero; the SH view direction held constant), on every route above, with no host sync; every other
 // output is unchanged, bit for bit.
+// `want_abs_grad` (not in the reference): BackwardOutput::dL_dmeans_2d_abs, the AbsGrad densification
+// signal, from the backward blend (cugs_rasterize_backward_abs), on every route above; every other output is the same
+// up to the order of the blend's atomic adds.
 
 // training/loss.hpp:21-52 + the autograd step of trainer.cpp:214-217 in two launches.
 // Scalars are 0-dim device tensors, as in the reference.
@@ -181,6 +189,7 @@ public:
     DensificationStats densify(ModelTensors& model, int step, const torch::Tensor& noise = {},
                                FusedAdam* optimizer = nullptr);
     void reset_opacity(ModelTensors& model);
+    const torch::Tensor& grad_accum() const { return grad_accum_; }     // [N] sum of the gradient norms since the last densify
 private:
     void reset_accumulators(int64_t n, const torch::Device& device);
     DensificationConfig config_;

@@ -388,6 +388,49 @@ __device__ __forceinline__ float reduce10r16(float cA, float cB, float v2, float
     return reduce_r16_tail(b0, b1, b2, lane);
 }
 
+// reduce12ar16: reduce10r16 with an ELEVENTH and TWELFTH value v10, v11 (the AbsGrad backward's two sums of absolute
+// per-pixel mean gradients).  Stage 1 gains a sixth pair a5 = v10 | v11 (two DPP adds); stage 2's
+// b2 = a4, which uses no bank selection in reduce10r16 - banks 0 and 1 both carry v7, banks 2 and 3 both v9 - takes
+// a4 | a5 with bank masks 0x5 / 0xa (one more DPP add).  Everything after it is unchanged: the v7 total lands in lanes
+// r = 1 and 3 of the row, v10 in r = 5 and 7, v9 in r = 9 and 11, v11 in r = 13 and 15.  17 DPP adds in stages 1 and 2.
+// Result, per row: as reduce10r16 plus r = 5 -> slot 10, r = 13 -> slot 11.  `with9` false (no depth route: the
+// caller passes v9 = 0): lane r = 9 is not designated either.
+__device__ __forceinline__ int reduce12ar16_slot(int lane, bool with9) {
+    const int r = lane & 15;
+    if (r == 5) return 10;
+    if (r == 13) return 11;
+    if (r == 9) return with9 ? 9 : -1;
+    return reduce9r16_slot(lane);
+}
+
+__device__ __forceinline__ float reduce12ar16(float cA, float cB, float v2, float v3, float v4, float v5, float v6,
+                                              float v8, float v7, float v9, float v10, float v11, int lane) {
+    float a0, a1, a2, a3, a4, a5, b0, b1, b2;
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %10, %9 row_mirror row_mask:0xf bank_mask:0xf\n\t"       // a0 = cA + mirror(cB)
+        "v_add_f32_dpp %1, %11, %11 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a1 = v2 | v3
+        "v_add_f32_dpp %1, %12, %12 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %2, %13, %13 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a2 = v4 | v5
+        "v_add_f32_dpp %2, %14, %14 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %3, %15, %15 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a3 = v6 | v8
+        "v_add_f32_dpp %3, %16, %16 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %4, %17, %17 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a4 = v7 | v9
+        "v_add_f32_dpp %4, %18, %18 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %5, %19, %19 row_mirror row_mask:0xf bank_mask:0x3\n\t"      // a5 = v10 | v11
+        "v_add_f32_dpp %5, %20, %20 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %6, %0, %0 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   // b0 = a0 | a1
+        "v_add_f32_dpp %6, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %8, %4, %4 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   // b2 = a4 | a5 (v7, v10, v9, v11 per bank)
+        "v_add_f32_dpp %8, %5, %5 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %7, %2, %2 row_half_mirror row_mask:0xf bank_mask:0x5\n\t"   // b1 = a2 | a3
+        "v_add_f32_dpp %7, %3, %3 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "s_nop 1\n\t"                                                               // the compiler's DPP reads b1 next
+        : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(a5), "=&v"(b0), "=&v"(b1), "=&v"(b2)
+        : "v"(cA), "v"(cB), "v"(v2), "v"(v3), "v"(v4), "v"(v5), "v"(v6), "v"(v8), "v"(v7), "v"(v9), "v"(v10), "v"(v11));
+    return reduce_r16_tail(b0, b1, b2, lane);
+}
+
 // reduce12r16: the transpose-reduce of TWELVE per-lane values inside each 16-lane DPP row (the camera-pose backward's
 // per-Gaussian rows, project_backward_kernels.h), in plain builtins - it runs once per workgroup, not per blend step, so
 // the selects cost nothing that matters.  Stage 1 row_mirror (side = lane bit 3): 12 -> 6; stage 2 row_half_mirror

@@ -80,7 +80,19 @@ __device__ __forceinline__ void block_excl3(uint32_t a, uint32_t b, uint32_t c, 
     __syncthreads();
 }
 
-// accumulate_gradients (densification.cpp:59-88)
+// accumulate_gradients (densification.cpp:59-88) for Gaussian i, whose 2-D gradient is the float2 at `g2`
+__device__ __forceinline__ void accumulate_one(int64_t i, const float2* __restrict__ g2,
+                                               const int32_t* __restrict__ radii, float* __restrict__ grad_accum,
+                                               float* __restrict__ grad_count, float* __restrict__ max_radii) {
+    const int r = radii[i];
+    if (r > 0) {                                                             // visible in this view (:70)
+        const float2 g = *g2;
+        grad_accum[i] += sqrtf(g.x * g.x + g.y * g.y);                        // ||dL/d(screen xy)||_2 (:76)
+        grad_count[i] += 1.0f;
+    }
+    max_radii[i] = fmaxf(max_radii[i], (float)r);                            // :86-87 (every Gaussian)
+}
+
 __global__ __launch_bounds__(CUGS_BLOCK) void k_accumulate(int64_t n, const float* __restrict__ dmeans,
                                                            const int32_t* __restrict__ radii,
                                                            float* __restrict__ grad_accum,
@@ -88,13 +100,18 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_accumulate(int64_t n, const floa
                                                            float* __restrict__ max_radii) {
     const int64_t i = (int64_t)blockIdx.x * CUGS_BLOCK + threadIdx.x;
     if (i >= n) return;
-    const int r = radii[i];
-    if (r > 0) {                                                             // visible in this view (:70)
-        const float2 g = reinterpret_cast<const float2*>(dmeans)[i];
-        grad_accum[i] += sqrtf(g.x * g.x + g.y * g.y);                        // ||dL/d(screen xy)||_2 (:76)
-        grad_count[i] += 1.0f;
-    }
-    max_radii[i] = fmaxf(max_radii[i], (float)r);                            // :86-87 (every Gaussian)
+    accumulate_one(i, reinterpret_cast<const float2*>(dmeans) + i, radii, grad_accum, grad_count, max_radii);
+}
+
+// the same with the gradient of Gaussian i at dmeans[i * stride + {0, 1}] (stride even: the float2 stays aligned)
+__global__ __launch_bounds__(CUGS_BLOCK) void k_accumulate_strided(int64_t n, const float* __restrict__ dmeans,
+                                                                   int64_t stride, const int32_t* __restrict__ radii,
+                                                                   float* __restrict__ grad_accum,
+                                                                   float* __restrict__ grad_count,
+                                                                   float* __restrict__ max_radii) {
+    const int64_t i = (int64_t)blockIdx.x * CUGS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    accumulate_one(i, reinterpret_cast<const float2*>(dmeans + i * stride), radii, grad_accum, grad_count, max_radii);
 }
 
 // compute_clone_mask / compute_split_mask / compute_keep_mask (densification.cpp:351-442)
@@ -253,6 +270,20 @@ extern "C" int cugs_densify_accumulate(int64_t n, const float* dL_dmeans_2d, con
     if ((reinterpret_cast<uintptr_t>(dL_dmeans_2d) & 7u) != 0) return CUGS_EALIGN;
     hipLaunchKernelGGL(k_accumulate, dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, static_cast<hipStream_t>(stream), n,
                        dL_dmeans_2d, radii, grad_accum, grad_count, max_radii_2d);
+    CUGS_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cugs_densify_accumulate_strided(int64_t n, const float* dL_dmeans_2d, int64_t row_stride_floats,
+                                               const int32_t* radii, float* grad_accum, float* grad_count,
+                                               float* max_radii_2d, void* stream) {
+    if (n < 0 || row_stride_floats < 2) return CUGS_EINVAL;
+    if (n == 0) return 0;
+    if (!dL_dmeans_2d || !radii || !grad_accum || !grad_count || !max_radii_2d) return CUGS_EINVAL;
+    // every row's pair is read as one float2
+    if ((reinterpret_cast<uintptr_t>(dL_dmeans_2d) & 7u) != 0 || (row_stride_floats & 1) != 0) return CUGS_EALIGN;
+    hipLaunchKernelGGL(k_accumulate_strided, dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, static_cast<hipStream_t>(stream), n,
+                       dL_dmeans_2d, row_stride_floats, radii, grad_accum, grad_count, max_radii_2d);
     CUGS_LAUNCH_CHECK();
     return 0;
 }

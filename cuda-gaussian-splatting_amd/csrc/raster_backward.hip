@@ -33,6 +33,9 @@
 // (G += dL/dD z: one FMA) and phase 2 forms a TENTH sum, sum weight * dL/dD = dL/dz, delivered to word 9 of the row by
 // reduce10r16.  dL/dA needs no per-step work: sum_i alpha_i T_i + final_T = 1, so the channel (c = 1, bg = 0) has the
 // gradient of (c = 0, bg = -1), which only enters D's starting value (D -= final_T dL/dA).
+// ABS (cugs_rasterize_backward_abs): the AbsGrad densification signal.  Phase 2 also forms, per
+// Gaussian, sum |dL/dpower (a dx + b dy)| and sum |dL/dpower (b dx + c dy)| over the pixels - the per-pixel summands of
+// dL/dmean2d with fabs around each - and reduce12ar16 delivers them to words 10 and 11 of the row.  Phase 1 is unchanged.
 // The summation order differs from any sequential order; the oracle accumulates in fp64.
 // Per-contribution VALUES (not decisions) use v_rcp_f32 and fused multiply-adds: 1 ulp-level
 // differences from the oracle's divisions, far inside the 1e-4 bar.
@@ -60,6 +63,9 @@ namespace {
 // Gaussians are flushed before the record batch they point into is re-staged.
 #define CUGS_BWD_HITS 4
 static_assert(CUGS_BWD_HITS == CUGS_HIT_GROUP, "a hit group is one flush");
+#ifndef CUGS_BWD_ABS_WAVES
+#define CUGS_BWD_ABS_WAVES 7         /* the ABS variants' occupancy target */
+#endif
 #ifndef CUGS_BWD_HSTRIDE
 #define CUGS_BWD_HSTRIDE 64        /* float2 per Gaussian block: the 64 pixels, no padding - see the LDS budget below */
 #endif
@@ -67,8 +73,9 @@ static_assert(CUGS_BWD_HITS == CUGS_HIT_GROUP, "a hit group is one flush");
 // WIDE: accumulator larger than 4 GiB (n > 2^26 rows): 64-bit scatter addresses.
 // STATS (dev builds only): step counters written to accumulator row `stats_row` (tools/ablate_backward.py).
 // DEPTH: the depth / alpha maps' gradients too (dL_ddepth_map, dL_dalpha: [H,W], either may be NULL = zero).
-template <bool PACKED, bool WIDE, bool STATS, bool DEPTH = false>
-__global__ __launch_bounds__(CUGS_BLOCK) __attribute__((amdgpu_waves_per_eu(DEPTH ? 7 : 8)))
+// ABS: the absolute 2-D mean gradients too (words 10, 11 of the row); with or without DEPTH.
+template <bool PACKED, bool WIDE, bool STATS, bool DEPTH = false, bool ABS = false>
+__global__ __launch_bounds__(CUGS_BLOCK) __attribute__((amdgpu_waves_per_eu(ABS ? CUGS_BWD_ABS_WAVES : (DEPTH ? 7 : 8))))
 void k_raster_backward(RasterGeom geo, RasterSrc src,
                                                                 const float* __restrict__ dL_dcolor,
                                                                 const float* __restrict__ final_T,
@@ -140,7 +147,7 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
         }
         eA[i] = side ? gg : r; eB[i] = side ? r : gg; e2[i] = bb; eZ[i] = zz;
     }
-    const int slot2 = DEPTH ? reduce10r16_slot(lane) : reduce9r16_slot(lane);
+    const int slot2 = ABS ? reduce12ar16_slot(lane, DEPTH) : DEPTH ? reduce10r16_slot(lane) : reduce9r16_slot(lane);
     const unsigned slot_off = (unsigned)(slot2 < 0 ? 0 : slot2) * 4u;
     unsigned long long hitrecs = 0ull;                       // record (float4) index of pending Gaussian h in bits [16h, 16h+16);
                                                              // stale slots of a partial flush stay valid indices
@@ -168,7 +175,14 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
         const int rec = (int)((hitrecs >> (16 * h2)) & 0xFFFFull);                     // float4 index of the record
         const float4* c4 = reinterpret_cast<const float4*>(&s_contrib[wave][h2][g2i * 4]);
         const float4 p01 = c4[0], p23 = c4[1];                                         // (weight, v3) x 4 pixels
-        const float2 mean = *reinterpret_cast<const float2*>(&s_rec[rec]);
+        float4 head;                                                                   // mean x, y (ABS: and a, b)
+        if (ABS) {
+            head = s_rec[rec];
+        } else {
+            const float2 m = *reinterpret_cast<const float2*>(&s_rec[rec]);
+            head = make_float4(m.x, m.y, 0.0f, 0.0f);
+        }
+        const float2 mean = make_float2(head.x, head.y);
         const float4 tail = s_rec[rec + 1];                                            // c, opacity, tau, index
         const float dy = py2 - mean.y;
         const float dx0 = px2 - mean.x, dx1 = dx0 + 1.0f, dx2 = dx0 + 2.0f, dx3 = dx0 + 3.0f;
@@ -186,7 +200,27 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
         M1 *= tail.y; Mxx *= tail.y;
         const float M1y = dy * oA, Myy = dy * M1y, Mxy = dy * M1;
         float total;
-        if (DEPTH) {
+        if (ABS) {
+            // |dL/dpower (a dx_k + b dy)| = |v3_k| |opacity| |a dx_k + b dy|, the same with (b, c): one FMA for the
+            // linear form, one multiply-add with both factors' sign bits cleared (source modifiers) per pixel and sum
+            const float bdy = head.w * dy, cdy = tail.x * dy;
+            float SX = fabsf(p01.y) * fabsf(fmaf(head.z, dx0, bdy));
+            float SY = fabsf(p01.y) * fabsf(fmaf(head.w, dx0, cdy));
+            SX = fmaf(fabsf(p01.w), fabsf(fmaf(head.z, dx1, bdy)), SX);
+            SY = fmaf(fabsf(p01.w), fabsf(fmaf(head.w, dx1, cdy)), SY);
+            SX = fmaf(fabsf(p23.y), fabsf(fmaf(head.z, dx2, bdy)), SX);
+            SY = fmaf(fabsf(p23.y), fabsf(fmaf(head.w, dx2, cdy)), SY);
+            SX = fmaf(fabsf(p23.w), fabsf(fmaf(head.z, dx3, bdy)), SX);
+            SY = fmaf(fabsf(p23.w), fabsf(fmaf(head.w, dx3, cdy)), SY);
+            const float ao = fabsf(tail.y);
+            SX *= ao; SY *= ao;
+            float RZ = 0.0f;
+            if (DEPTH) {
+                RZ = p01.x * eZ[0];
+                RZ = fmaf(p01.z, eZ[1], RZ); RZ = fmaf(p23.x, eZ[2], RZ); RZ = fmaf(p23.z, eZ[3], RZ);
+            }
+            total = reduce12ar16(RA, RB, R2, A, M1, M1y, Mxx, Myy, Mxy, RZ, SX, SY, lane);
+        } else if (DEPTH) {
             float RZ = p01.x * eZ[0];
             RZ = fmaf(p01.z, eZ[1], RZ); RZ = fmaf(p23.x, eZ[2], RZ); RZ = fmaf(p23.z, eZ[3], RZ);
             total = reduce10r16(RA, RB, R2, A, M1, M1y, Mxx, Myy, Mxy, RZ, lane);
@@ -307,8 +341,8 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
 
 // grad_accum rows -> the four reference-layout tensors of RasterizeBackwardOutput (backward.hpp); applies the
 // per-Gaussian map from the accumulated moments (see the header comment) with Sigma'^-1 = (a, b, c).
-// DEPTH: also dL_ddepths [n] from word 9.
-template <bool PACKED, bool DEPTH = false>
+// DEPTH: also dL_ddepths [n] from word 9.  ABS: also dL_dmeans_abs [n,2] from words 10 and 11.
+template <bool PACKED, bool DEPTH = false, bool ABS = false>
 __global__ __launch_bounds__(CUGS_BLOCK) void k_unpack_grads(int64_t n, const float* __restrict__ acc,
                                                              const float* __restrict__ packed,
                                                              const float* __restrict__ cov_2d_inv,
@@ -316,13 +350,19 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_unpack_grads(int64_t n, const fl
                                                              float* __restrict__ dL_dopa,
                                                              float* __restrict__ dL_dmeans,
                                                              float* __restrict__ dL_dcov,
-                                                             float* __restrict__ dL_ddepths) {
+                                                             float* __restrict__ dL_ddepths,
+                                                             float* __restrict__ dL_dmeans_abs) {
     const int64_t i = (int64_t)blockIdx.x * CUGS_BLOCK + threadIdx.x;
     if (i >= n) return;
     const float4* row = reinterpret_cast<const float4*>(acc + i * CUGS_GRAD_STRIDE);
     const float4 r0 = row[0], r1 = row[1];
     float r2;
-    if (DEPTH) {
+    if (ABS) {
+        const float4 w = row[2];                                                    // M2yy, dL_dz, abs x, abs y
+        r2 = w.x;
+        if (DEPTH) dL_ddepths[i] = w.y;
+        *reinterpret_cast<float2*>(dL_dmeans_abs + i * 2) = make_float2(w.z, w.w);
+    } else if (DEPTH) {
         const float2 w89 = *reinterpret_cast<const float2*>(acc + i * CUGS_GRAD_STRIDE + 8);
         r2 = w89.x;
         dL_ddepths[i] = w89.y;
@@ -358,7 +398,8 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
                                        float* dL_dcov_2d_inv, bool prezeroed, const uint32_t* tile_order, void* stream,
                                        bool depth_map = false, const float* depths = nullptr,
                                        const float* dL_ddepth_map = nullptr, const float* dL_dalpha = nullptr,
-                                       float* dL_ddepths = nullptr) {
+                                       float* dL_ddepths = nullptr, bool abs_grad = false,
+                                       float* dL_dmeans_2d_abs = nullptr) {
     if (width < 0 || height < 0 || n < 0 || !background_host) return CUGS_EINVAL;
     if (n == 0) return 0;
     if (!grad_accum) return CUGS_EINVAL;
@@ -367,6 +408,8 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
                       (dL_dcov_2d_inv != nullptr);
     if (n_soa != 0 && n_soa != 4) return CUGS_EINVAL;
     if (depth_map && (n_soa == 4) != (dL_ddepths != nullptr)) return CUGS_EINVAL;   // dL_ddepths with the four, not alone
+    if (!depth_map && dL_ddepths) return CUGS_EINVAL;                               // ... and on the depth route only
+    if (abs_grad && (n_soa == 4) != (dL_dmeans_2d_abs != nullptr)) return CUGS_EINVAL;   // the same for the absolute tensor
     if (n_soa == 4 && !packed && !cov_2d_inv) return CUGS_EINVAL;
     if (packed && !cugs_aligned16(packed)) return CUGS_EALIGN;
     if (tile_order && !cugs_aligned16(tile_order)) return CUGS_EALIGN;
@@ -398,7 +441,22 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
 #define CUGS_LAUNCH_BWD_DEPTH(P, W)                                                                                  \
     hipLaunchKernelGGL((k_raster_backward<P, W, false, true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, \
                        dL_dcolor, final_T, n_contrib, grad_accum, stats_arg, depths, dL_ddepth_map, dL_dalpha)
-        if (depth_map) {                                        // no step counters on this route
+#define CUGS_LAUNCH_BWD_ABS(P, W, D)                                                                              \
+    hipLaunchKernelGGL((k_raster_backward<P, W, false, D, true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, \
+                       dL_dcolor, final_T, n_contrib, grad_accum, stats_arg, depths, dL_ddepth_map, dL_dalpha)
+        if (abs_grad) {                                         // no step counters on these routes either
+            if (depth_map) {
+                if (packed) {
+                    if (wide) CUGS_LAUNCH_BWD_ABS(true, true, true); else CUGS_LAUNCH_BWD_ABS(true, false, true);
+                } else {
+                    if (wide) CUGS_LAUNCH_BWD_ABS(false, true, true); else CUGS_LAUNCH_BWD_ABS(false, false, true);
+                }
+            } else if (packed) {
+                if (wide) CUGS_LAUNCH_BWD_ABS(true, true, false); else CUGS_LAUNCH_BWD_ABS(true, false, false);
+            } else {
+                if (wide) CUGS_LAUNCH_BWD_ABS(false, true, false); else CUGS_LAUNCH_BWD_ABS(false, false, false);
+            }
+        } else if (depth_map) {                                 // no step counters on this route
             if (packed) {
                 if (wide) CUGS_LAUNCH_BWD_DEPTH(true, true); else CUGS_LAUNCH_BWD_DEPTH(true, false);
             } else {
@@ -417,19 +475,30 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
         }
 #undef CUGS_LAUNCH_BWD
 #undef CUGS_LAUNCH_BWD_DEPTH
+#undef CUGS_LAUNCH_BWD_ABS
         CUGS_LAUNCH_CHECK();
     }
     if (n_soa == 4) {
         const dim3 grid((unsigned)((n + CUGS_BLOCK - 1) / CUGS_BLOCK));
 #define CUGS_LAUNCH_UNPACK(P, D)                                                                                 \
     hipLaunchKernelGGL((k_unpack_grads<P, D>), grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed, cov_2d_inv, \
-                       dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, dL_ddepths)
-        if (depth_map) {
+                       dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, dL_ddepths, nullptr)
+#define CUGS_LAUNCH_UNPACK_ABS(P, D)                                                                                   \
+    hipLaunchKernelGGL((k_unpack_grads<P, D, true>), grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed, cov_2d_inv, \
+                       dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, dL_ddepths, dL_dmeans_2d_abs)
+        if (abs_grad) {
+            if (depth_map) {
+                if (packed) CUGS_LAUNCH_UNPACK_ABS(true, true); else CUGS_LAUNCH_UNPACK_ABS(false, true);
+            } else {
+                if (packed) CUGS_LAUNCH_UNPACK_ABS(true, false); else CUGS_LAUNCH_UNPACK_ABS(false, false);
+            }
+        } else if (depth_map) {
             if (packed) CUGS_LAUNCH_UNPACK(true, true); else CUGS_LAUNCH_UNPACK(false, true);
         } else {
             if (packed) CUGS_LAUNCH_UNPACK(true, false); else CUGS_LAUNCH_UNPACK(false, false);
         }
 #undef CUGS_LAUNCH_UNPACK
+#undef CUGS_LAUNCH_UNPACK_ABS
         CUGS_LAUNCH_CHECK();
     }
     return 0;
@@ -493,6 +562,23 @@ extern "C" int cugs_rasterize_backward_depth(int width, int height, const float 
                                    depths, dL_ddepth_map, dL_dalpha, dL_ddepths);
 }
 
+extern "C" int cugs_rasterize_backward_abs(int width, int height, const float background_host[3],
+                                           const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                           const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                           const float* opacities_act, const float* packed,
+                                           const float* dL_dcolor, const float* final_T,
+                                           const int32_t* n_contrib, int64_t n, float* grad_accum,
+                                           float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                           float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
+                                           const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
+                                           float* dL_ddepths, float* dL_dmeans_2d_abs, void* stream) {
+    const bool depth_map = depths || dL_ddepth_map || dL_dalpha;          // all NULL: the colour-only ABS kernel
+    return rasterize_backward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
+                                   opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
+                                   dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, prezeroed != 0, tile_order, stream,
+                                   depth_map, depths, dL_ddepth_map, dL_dalpha, dL_ddepths, true, dL_dmeans_2d_abs);
+}
+
 #ifdef CUGS_DEV
 // ---- development hooks (libcugs_hip_dev.so only; not part of include/cugs_hip.h) ------------------
 // cugsdbg_reduce9: one wave runs reduce9t on caller data.  in: [9][64] floats (value k of lane l at k*64+l,
@@ -525,6 +611,18 @@ __global__ void k_dbg_reduce10r16(const float* __restrict__ in, float* __restric
     out[l] = reduce10r16(side ? v1 : v0, side ? v0 : v1, in[2 * 64 + l], in[3 * 64 + l], in[4 * 64 + l], in[5 * 64 + l],
                          in[6 * 64 + l], in[8 * 64 + l], in[7 * 64 + l], in[9 * 64 + l], l);
     slots[l] = reduce10r16_slot(l);
+}
+// reduce12ar16: in [12][64] (value k of lane l at k*64+l), out [64], slots [64] (with the depth slot 9), slots_nodepth [64]
+__global__ void k_dbg_reduce12ar16(const float* __restrict__ in, float* __restrict__ out, int* __restrict__ slots,
+                                   int* __restrict__ slots_nodepth) {
+    const int l = threadIdx.x;
+    const bool side = (l & 8) != 0;
+    const float v0 = in[0 * 64 + l], v1 = in[1 * 64 + l];
+    out[l] = reduce12ar16(side ? v1 : v0, side ? v0 : v1, in[2 * 64 + l], in[3 * 64 + l], in[4 * 64 + l], in[5 * 64 + l],
+                          in[6 * 64 + l], in[8 * 64 + l], in[7 * 64 + l], in[9 * 64 + l], in[10 * 64 + l], in[11 * 64 + l],
+                          l);
+    slots[l] = reduce12ar16_slot(l, true);
+    slots_nodepth[l] = reduce12ar16_slot(l, false);
 }
 __global__ void k_dbg_rcp(const float* __restrict__ in, float* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -582,6 +680,12 @@ extern "C" int cugsdbg_reduce9r16(const float* in, float* out, int* slots, void*
 }
 extern "C" int cugsdbg_reduce10r16(const float* in, float* out, int* slots, void* stream) {
     hipLaunchKernelGGL(k_dbg_reduce10r16, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), in, out, slots);
+    CUGS_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int cugsdbg_reduce12ar16(const float* in, float* out, int* slots, int* slots_nodepth, void* stream) {
+    hipLaunchKernelGGL(k_dbg_reduce12ar16, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), in, out, slots,
+                       slots_nodepth);
     CUGS_LAUNCH_CHECK();
     return 0;
 }

@@ -93,15 +93,29 @@ class DensificationController:
         self.grad_accum_, self.grad_count_, self.max_radii_2d_ = z(), z(), z()
 
     def accumulate_gradients(self, dL_dmeans_2d: torch.Tensor, radii: torch.Tensor) -> None:
-        """densification.cpp:59-88 as one launch, no host sync."""
+        """densification.cpp:59-88 as one launch, no host sync.
+        `dL_dmeans_2d` [N,2] float32 may be a strided view whose last stride is 1 and whose row stride is even and at
+        least 2: it is read in place (cugs_densify_accumulate_strided), with no copy.  A host that wants AbsGrad (AbsGS)
+        densification passes BackwardOutput.dL_dmeans_2d_abs (render_backward(..., want_abs_grad=True)) here instead of
+        dL_dmeans_2d.  The accumulated norm is then a sum of absolute per-pixel gradients, which is on a different,
+        larger scale than the signed one: config.grad_threshold has to be chosen for it (AbsGS and gsplat's `absgrad`
+        use about 0.0008 where the signed default is 0.0002); DensificationConfig's default is the signed one."""
         _torch_check(dL_dmeans_2d.is_cuda and radii.is_cuda, "accumulate_gradients: tensors must be on CUDA")
         _torch_check(dL_dmeans_2d.dim() == 2 and dL_dmeans_2d.shape[1] == 2, "dL_dmeans_2d must be [N, 2]")
         n = int(dL_dmeans_2d.shape[0])
         _torch_check(radii.numel() == n, "radii must be [N]")
         if self.grad_accum_ is None or self.grad_accum_.shape[0] != n or self.grad_accum_.device != dL_dmeans_2d.device:
             self.reset_accumulators(n, dL_dmeans_2d.device)
-        g = dL_dmeans_2d.contiguous().to(torch.float32)
         r = radii.contiguous().to(torch.int32)
+        g = dL_dmeans_2d
+        row = int(g.stride(0)) if n > 0 else 2
+        if (g.dtype == torch.float32 and not g.is_contiguous() and g.stride(1) == 1 and row >= 2 and row % 2 == 0
+                and g.data_ptr() % 8 == 0):
+            check(lib.cugs_densify_accumulate_strided(n, _ptr(g), row, _ptr(r), _ptr(self.grad_accum_),
+                                                      _ptr(self.grad_count_), _ptr(self.max_radii_2d_),
+                                                      _stream(g.device)), "cugs_densify_accumulate_strided")
+            return
+        g = dL_dmeans_2d.contiguous().to(torch.float32)
         check(lib.cugs_densify_accumulate(n, _ptr(g), _ptr(r), _ptr(self.grad_accum_), _ptr(self.grad_count_),
                                           _ptr(self.max_radii_2d_), _stream(g.device)), "cugs_densify_accumulate")
 

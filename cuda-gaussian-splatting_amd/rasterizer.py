@@ -509,7 +509,8 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
                        zeroed_accum: Optional[torch.Tensor] = None,
                        tile_order: Optional[torch.Tensor] = None, depths: Optional[torch.Tensor] = None,
                        dL_ddepth_map: Optional[torch.Tensor] = None,
-                       dL_dalpha: Optional[torch.Tensor] = None) -> RasterizeBackwardOutput:
+                       dL_dalpha: Optional[torch.Tensor] = None,
+                       want_abs_grad: bool = False) -> RasterizeBackwardOutput:
     """`zeroed_accum` (optional, not in the reference): an [N, 16] accumulator that is already all zeros (cleared by
     rasterize_forward(..., zero_buf=...)): used as is, without the fill.
     `tile_order` (optional, not in the reference): as in rasterize_forward; the sums are the same up to the order of
@@ -517,7 +518,12 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
     `depths`, `dL_ddepth_map`, `dL_dalpha` (optional, not in the reference): the gradients of the depth map
     (rasterize_forward(..., depths=...)) and of the alpha map 1 - final_T, [H,W] each, either may be None (zero);
     `depths` is required with either (cugs_rasterize_backward_depth).  They add to the opacity and 2-D gradients; dL/dz
-    goes to word 9 of each accumulator row and, unpacked, to RasterizeBackwardOutput.dL_ddepths."""
+    goes to word 9 of each accumulator row and, unpacked, to RasterizeBackwardOutput.dL_ddepths.
+    `want_abs_grad=True` (not in the reference): the blend also sums the ABSOLUTE value of every
+    per-pixel 2-D mean gradient (AbsGS / `absgrad`) into words 10 and 11 of each row (cugs_rasterize_backward_abs), with
+    or without the depth arguments.  RasterizeBackwardOutput.dL_dmeans_2d_abs is [N,2]: its own tensor when unpacked,
+    the [:, 10:12] view of grad_accum with unpack=False.  Every other output is the same up to the order of the atomic
+    adds."""
     _torch_check(dL_dcolor.is_cuda, "dL_dcolor must be on CUDA")
     dev = dL_dcolor.device
     n = int(n_gaussians)
@@ -542,10 +548,27 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
     else:
         d_rgb = d_opa = d_means = d_cov = None
     d_z = torch.empty((n,), **f) if unpack and depth_route else None
+    d_abs = None
+    if want_abs_grad:
+        d_abs = torch.empty((n, 2), **f) if unpack else accum[:, 10:12]
     if n > 0 and tile_order is not None:
         _torch_check(tile_order.is_contiguous() and tile_order.dtype == torch.int32 and
                      tile_order.numel() == 4 * tile_ranges.shape[0], "tile_order must be a contiguous [tiles, 4] int32 tensor")
-    if n > 0 and depth_route:
+    if n > 0 and want_abs_grad:
+        bg = (C.c_float * 3)(*[float(b) for b in background])
+        f32 = lambda t: None if t is None else _f32c(t)
+        check(lib.cugs_rasterize_backward_abs(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
+                                              _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
+                                              _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
+                                              _ptr(opacities.contiguous()), _ptr(packed),
+                                              _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
+                                              _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
+                                              _ptr(d_means), _ptr(d_cov), 1 if zeroed_accum is not None else 0,
+                                              _ptr(tile_order), _ptr(f32(depths)), _ptr(f32(dL_ddepth_map)),
+                                              _ptr(f32(dL_dalpha)), _ptr(d_z), _ptr(d_abs) if unpack else None,
+                                              _stream(dev)),
+              "cugs_rasterize_backward_abs")
+    elif n > 0 and depth_route:
         bg = (C.c_float * 3)(*[float(b) for b in background])
         f32 = lambda t: None if t is None else _f32c(t)
         check(lib.cugs_rasterize_backward_depth(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
@@ -577,7 +600,7 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
                                           _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
                                           _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
                                           _ptr(d_means), _ptr(d_cov), _stream(dev)), "cugs_rasterize_backward")
-    return RasterizeBackwardOutput(d_rgb, d_opa, d_means, d_cov, accum, dL_ddepths=d_z)
+    return RasterizeBackwardOutput(d_rgb, d_opa, d_means, d_cov, accum, dL_ddepths=d_z, dL_dmeans_2d_abs=d_abs)
 
 
 def project_backward(dL_dmeans_2d: Optional[torch.Tensor], dL_dcov_2d_inv: Optional[torch.Tensor],
@@ -758,7 +781,8 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                     geom_flat: Optional[torch.Tensor] = None, fused_adam=None, on_gated_ready=None,
                     mcmc=None, mcmc_step: int = 0, mcmc_noise: Optional[torch.Tensor] = None,
                     dL_ddepth_map: Optional[torch.Tensor] = None,
-                    dL_dalpha: Optional[torch.Tensor] = None, want_camera_grad: bool = False) -> BackwardOutput:
+                    dL_dalpha: Optional[torch.Tensor] = None, want_camera_grad: bool = False,
+                    want_abs_grad: bool = False) -> BackwardOutput:
     """`dL_drgb_gated_out` ([N,3], optional, not in the reference): when given, the per-view SH gradient
     is NOT materialised (dL_dsh_coeffs is None) and the gated colour gradient is written there instead,
     for parallel.exchange_gradients() to rebuild the summed SH gradient after the all-gather.
@@ -782,7 +806,14 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
     gradients (two small reduction launches follow it; no host sync).  The SH view direction is held constant, as it is
     for dL_dpositions.  Plain and fused (fused_adam, mcmc) routes, with or without the depth / alpha map gradients; every
     other output is unchanged, bit for bit; pose.viewmat_grad_to_se3 turns it into a 6-vector.  Not with the
-    data-parallel arguments."""
+    data-parallel arguments.
+    `want_abs_grad=True` (not in the reference): BackwardOutput.dL_dmeans_2d_abs, the AbsGrad (AbsGS)
+    densification signal - per Gaussian, the sum over its pixels of the ABSOLUTE value of each per-pixel summand of
+    dL_dmeans_2d, which large splats over fine detail do not cancel away.  It comes from the backward blend, so it works
+    on every route (plain, fused_adam, mcmc, want_camera_grad, the depth / alpha map gradients, the data-parallel
+    arguments).  It is an [N,2] float32 VIEW of the blend's accumulator rows (row stride 16 floats, no copy; it keeps
+    the rows alive): pass it to DensificationController.accumulate_gradients as it is.  Every other output is the same
+    up to the order of the blend's atomic adds.  Without the flag the field is None and nothing changes."""
     _torch_check(dL_dcolor.is_cuda, "dL_dcolor must be on CUDA device")
     _torch_check(dL_dcolor.dim() == 3 and dL_dcolor.shape[2] == 3, "dL_dcolor must be [H, W, 3]")
     depth_grads = dL_ddepth_map is not None or dL_dalpha is not None
@@ -808,7 +839,8 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
         return BackwardOutput(torch.zeros((0, 3), **f), torch.zeros((0, 4), **f), torch.zeros((0, 3), **f),
                               torch.zeros((0, 1), **f), torch.zeros_like(model.sh_coeffs),
                               torch.zeros((0, 2), **f),
-                              dL_dviewmat=torch.zeros((4, 4), **f) if want_camera_grad else None)
+                              dL_dviewmat=torch.zeros((4, 4), **f) if want_camera_grad else None,
+                              dL_dmeans_2d_abs=torch.zeros((0, 2), **f) if want_abs_grad else None)
     active_degree = min(int(settings.active_sh_degree), model.max_sh_degree())
     render_out.wait()                                    # a deferred render: read the pair count now (may raise)
     # the accumulator render() had the forward blend clear is good for ONE backward
@@ -825,7 +857,7 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                             settings.background, n, packed=render_out.packed, unpack=False, zeroed_accum=zeroed,
                             tile_order=getattr(render_out, "tile_order", None),
                             depths=render_out.depths if depth_grads else None, dL_ddepth_map=dL_ddepth_map,
-                            dL_dalpha=dL_dalpha)
+                            dL_dalpha=dL_dalpha, want_abs_grad=want_abs_grad)
     d_means_2d = torch.empty((n, 2), **f)
     if fused_adam is not None:
         _torch_check(fused_adam.model_ is model, "fused_adam must have been built on this model")
@@ -857,7 +889,8 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                   "cugs_project_backward_adam_pose")
         else:
             check(lib.cugs_project_backward_adam(*args, _ptr(d_means_2d), _stream(dev)), "cugs_project_backward_adam")
-        return BackwardOutput(None, None, None, None, None, d_means_2d, dL_dviewmat=d_view)
+        return BackwardOutput(None, None, None, None, None, d_means_2d, dL_dviewmat=d_view,
+                              dL_dmeans_2d_abs=rb.dL_dmeans_2d_abs)
     _torch_check(mcmc is None, "the fused MCMC route needs fused_adam (otherwise: compute_regularization, "
                  "step, inject_noise)")
     gated_by_projection = dL_drgb_gated_out
@@ -873,4 +906,5 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                           skip_sh_grad=dL_drgb_gated_out is not None, geom_flat=geom_flat,
                           want_camera_grad=want_camera_grad)
     return BackwardOutput(pb.dL_dpositions, pb.dL_drotations, pb.dL_dscales, pb.dL_dopacities,
-                          pb.dL_dsh_coeffs, d_means_2d, geom_flat=geom_flat, dL_dviewmat=pb.dL_dviewmat)
+                          pb.dL_dsh_coeffs, d_means_2d, geom_flat=geom_flat, dL_dviewmat=pb.dL_dviewmat,
+                          dL_dmeans_2d_abs=rb.dL_dmeans_2d_abs)

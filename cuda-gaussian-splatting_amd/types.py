@@ -174,6 +174,7 @@ class RasterizeBackwardOutput:
     dL_dcov_2d_inv: torch.Tensor
     grad_accum: Optional[torch.Tensor] = None   # [N,16] packed rows (not in the reference)
     dL_ddepths: Optional[torch.Tensor] = None   # [N] dL/dz of the depth map (rasterize_backward(..., depths=...), unpacked)
+    dL_dmeans_2d_abs: Optional[torch.Tensor] = None   # [N,2] AbsGrad sums (rasterize_backward(..., want_abs_grad=True))
 
 
 @dataclass
@@ -248,3 +249,6 @@ class BackwardOutput:
     dL_dmeans_2d: torch.Tensor
     geom_flat: Optional[torch.Tensor] = None    # [11N] buffer the four geometry gradients are views of (DP exchange)
     dL_dviewmat: Optional[torch.Tensor] = None  # [4,4] dL/d(world-to-camera matrix), render_backward(want_camera_grad=True)
+    # [N,2] absolute 2-D mean gradients (AbsGrad), render_backward(want_abs_grad=True): a view of words 10, 11 of the
+    # blend's accumulator rows (row stride 16), which it keeps alive; feed it to accumulate_gradients as it is
+    dL_dmeans_2d_abs: Optional[torch.Tensor] = None

@@ -258,10 +258,14 @@ int cugs_rasterize_forward_depth(int width, int height, const float background_h
 
 /* ---- a7: rasterize_backward (backward.cu:239-306, kernel :31-233) -------------------
  * grad_accum: [n,CUGS_GRAD_STRIDE] floats, 64-byte aligned scratch (zeroed by the callee).  A row is
- *   {dL_drgb[3], dL_dopacity_act, M1x, M1y, M2xx, M2xy, M2yy, dL_dz, 0...}
+ *   {dL_drgb[3], dL_dopacity_act, M1x, M1y, M2xx, M2xy, M2yy, dL_dz, abs_x, abs_y, 0...}
  * Word 9, dL_dz, is the gradient of the depth map with respect to the Gaussian's camera-space depth z (= depths[i]):
  * written by cugs_rasterize_backward_depth only, 0 otherwise.  cugs_project_backward and its fused variants add it to
  * dL/dt.z (t = W p + t_cam), i.e. dL_dpositions += dL_dz * W[2,:], for radii > 0 - a zero word changes no bit.
+ * Words 10 and 11, abs_x and abs_y, are the ABSOLUTE 2-D mean gradients (AbsGrad): the per-pixel summands of
+ * dL_dmeans_2d with fabs around each, abs_x = sum_p |dL/dpower (a dx + b dy)|, abs_y = sum_p |dL/dpower (b dx + c dy)|:
+ * written by cugs_rasterize_backward_abs only, 0 otherwise.  They are final, and no other entry point reads them but
+ * cugs_densify_accumulate_strided when it is pointed at them.
  * Words 4..8 are NOT gradients: they are the MOMENTS of dL/dpower over the pixel offsets d = pixel centre - mean,
  *   M1 = sum dL/dpower * (dx, dy),   M2 = sum dL/dpower * (dx^2, dx dy, dy^2),
  * from which the reference's two tensors follow by a per-Gaussian linear map with Sigma'^-1 = (a, b, c)
@@ -318,6 +322,26 @@ int cugs_rasterize_backward_depth(int width, int height, const float background_
                                   float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
                                   const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
                                   float* dL_ddepths, void* stream);
+
+/* cugs_rasterize_backward_depth that also accumulates the ABSOLUTE 2-D mean gradients (AbsGS / `absgrad`; not in the
+ * reference) into words 10 and 11 of each row (layout above): for every contribution the backward blend
+ * evaluates, after the gates Q1-Q3 and the clamp gate, the summand of dL_dmeans_2d with fabs around each component.
+ * Both are >= 0, and 0 for a Gaussian without a contribution.  depths, dL_ddepth_map and dL_dalpha may ALL be NULL: the
+ * colour-only blend (cugs_rasterize_backward_ordered's sums); otherwise they follow cugs_rasterize_backward_depth, and
+ * dL/dpower includes the depth and alpha map terms.  dL_dmeans_2d_abs [n,2] receives words 10 and 11 and is required
+ * exactly when the four reference-layout outputs are given; dL_ddepths exactly when they are given on the depth route
+ * (CUGS_EINVAL otherwise, before anything is queued).  Every other output is that of the entry this one extends, up to
+ * the order of the atomic adds. */
+int cugs_rasterize_backward_abs(int width, int height, const float background_host[3],
+                                const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                const float* opacities_act, const float* packed,
+                                const float* dL_dcolor, const float* final_T,
+                                const int32_t* n_contrib, int64_t n, float* grad_accum,
+                                float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
+                                const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
+                                float* dL_ddepths, float* dL_dmeans_2d_abs, void* stream);
 
 /* ---- a8+a9: project_backward (projection_backward.cu:253-344, kernel :26-247) -------
  * One launch: k_project_backward + directions + k_evaluate_sh_backward.  The incoming 2-D
@@ -420,6 +444,10 @@ int cugs_combined_loss(int width, int height, const float* rendered, const float
  * cugs_densify_accumulate: DensificationController::accumulate_gradients (densification.cpp:59-88), one
  *   launch, no host sync: for radii > 0, grad_accum += ||dL_dmeans_2d||_2 and grad_count += 1; for every
  *   Gaussian max_radii_2d = max(max_radii_2d, radii).  All three accumulators are float [n].
+ * cugs_densify_accumulate_strided: the same, bit for bit, reading Gaussian i's gradient at
+ *   dL_dmeans_2d[i * row_stride_floats + {0, 1}] (row_stride_floats >= 2, CUGS_EINVAL otherwise; even and the base
+ *   8-byte aligned, CUGS_EALIGN otherwise): pointed at word 10 of cugs_rasterize_backward_abs's rows with stride
+ *   CUGS_GRAD_STRIDE it accumulates the AbsGrad norm with no intermediate tensor.
  * cugs_densify_classify: compute_clone_mask / compute_split_mask / compute_keep_mask (:351-442) as one
  *   byte per Gaussian: bit 0 clone candidate, bit 1 split candidate, bit 2 keep.  The thresholds are the
  *   reference's float products (size = percent_dense * scene_extent, ws = 0.1f * scene_extent);
@@ -447,6 +475,9 @@ typedef struct cugs_densify_array {
 } cugs_densify_array;
 int cugs_densify_accumulate(int64_t n, const float* dL_dmeans_2d, const int32_t* radii, float* grad_accum,
                             float* grad_count, float* max_radii_2d, void* stream);
+int cugs_densify_accumulate_strided(int64_t n, const float* dL_dmeans_2d, int64_t row_stride_floats,
+                                    const int32_t* radii, float* grad_accum, float* grad_count, float* max_radii_2d,
+                                    void* stream);
 int cugs_densify_classify(int64_t n, const float* grad_accum, const float* grad_count, const float* max_radii_2d,
                           const float* scales, const float* opacities, float grad_threshold, float size_threshold,
                           float opacity_threshold, int apply_size_pruning, float max_screen_size,
