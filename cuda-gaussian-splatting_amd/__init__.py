@@ -25,4 +25,5 @@ from .pose import apply_se3, se3_exp, viewmat_grad_to_se3  # noqa: F401
 from . import pose  # noqa: F401
 from .ply_io import read_gaussian_ply, restore_optimizer, write_gaussian_ply  # noqa: F401
 from .views import StreamedViewCache, ViewCache, image_to_float, load_image_resized, load_image_u8  # noqa: F401
+from .metrics import EvalResults, ImageMetrics, compute_psnr, compute_ssim, eval_metrics, evaluate  # noqa: F401
 from . import parallel, scene  # noqa: F401

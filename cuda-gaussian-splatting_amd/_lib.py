@@ -125,6 +125,8 @@ SIGNATURES = {
     "cugs_fused_adam_groups": (_I, [C.POINTER(AdamGroup), _I, _F, _F, _F, _F, _F, _P]),
     "cugs_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_combined_loss": (_I, [_I, _I, _P, _P, _F, _I, _P, C.c_size_t, _P, _P, _P, _P]),
+    "cugs_eval_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "cugs_eval_metrics": (_I, [_I, _I, _P, _P, _P, _I, _P, C.c_size_t, _P, _P]),
     "cugs_densify_accumulate": (_I, [_L, _P, _P, _P, _P, _P, _P]),
     "cugs_densify_accumulate_strided": (_I, [_L, _P, _L, _P, _P, _P, _P, _P]),
     "cugs_densify_classify": (_I, [_L, _P, _P, _P, _P, _P, _F, _F, _F, _I, _F, _F, _P, _P, _P]),

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -879,6 +880,93 @@ torch::Tensor image_to_float(const torch::Tensor& view_u8, int width, int height
     check(cugs_image_to_float(static_cast<int>(src.size(1)), static_cast<int>(src.size(0)), src.data_ptr<uint8_t>(), width,
                               height, dst.data_ptr<float>(), stream_of(src)), "cugs_image_to_float");
     return dst;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Evaluation metrics (training/metrics.cpp)
+// ---------------------------------------------------------------------------------------------
+namespace {
+torch::Tensor run_eval(const torch::Tensor& rendered, const torch::Tensor& target, const torch::Tensor& out_in,
+                       int window_size, const char* who) {
+    TORCH_CHECK(rendered.sizes() == target.sizes(), who, ": rendered and target must have same shape");   // metrics.cpp:22-25
+    TORCH_CHECK(rendered.dim() == 3 && rendered.size(2) == 3, who, ": expected [H, W, 3] tensors");
+    TORCH_CHECK(rendered.dtype() == torch::kFloat32, who, ": rendered must be float32, got ", rendered.dtype());
+    TORCH_CHECK(target.dtype() == torch::kFloat32 || target.dtype() == torch::kUInt8, who,
+                ": target must be float32 or uint8, got ", target.dtype());
+    TORCH_CHECK(rendered.is_cuda() && target.is_cuda(), who, ": rendered and target must be on a CUDA device");
+    TORCH_CHECK(rendered.device() == target.device(), who, ": rendered and target must be on the same device");
+    TORCH_CHECK(window_size % 2 == 1, "window_size must be odd, got ", window_size);
+    TORCH_CHECK(window_size >= 3 && window_size <= 15, "window_size must be in 3..15, got ", window_size);
+    torch::Tensor out = out_in;
+    if (!out.defined()) {
+        out = torch::empty({4}, fopt(rendered));
+    } else {
+        TORCH_CHECK(out.dtype() == torch::kFloat32 && out.device() == rendered.device() && out.numel() == 4 &&
+                    out.is_contiguous(), who, ": out must be a contiguous float32 [4] on the images' device");
+    }
+    const int h = static_cast<int>(rendered.size(0)), w = static_cast<int>(rendered.size(1));
+    auto r = rendered.contiguous(), t = target.contiguous();
+    const bool f32 = t.dtype() == torch::kFloat32;
+    auto ws = workspace(rendered.device(), cugs_eval_workspace_bytes(w, h), 8);
+    check(cugs_eval_metrics(w, h, ptr<float>(r), f32 ? ptr<float>(t) : nullptr, f32 ? nullptr : ptr<uint8_t>(t),
+                            window_size, ws.data_ptr(), ws.numel(), ptr<float>(out), stream_of(rendered)),
+          "cugs_eval_metrics");
+    return out;
+}
+}  // namespace
+
+torch::Tensor eval_metrics(const torch::Tensor& rendered, const torch::Tensor& target, const torch::Tensor& out,
+                           int window_size) {
+    return run_eval(rendered, target, out, window_size, "eval_metrics");
+}
+float psnr_from_mse(float mse) {                                  // metrics.cpp:27-34
+    if (mse < 1e-10f) return 100.0f;
+    return 10.0f * std::log10(1.0f / mse);
+}
+float compute_psnr(const torch::Tensor& rendered, const torch::Tensor& target) {
+    return psnr_from_mse(run_eval(rendered, target, {}, 11, "PSNR").cpu().data_ptr<float>()[0]);
+}
+float compute_ssim(const torch::Tensor& rendered, const torch::Tensor& target) {
+    return run_eval(rendered, target, {}, 11, "SSIM").cpu().data_ptr<float>()[1];
+}
+
+EvalResults evaluate(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                     const std::vector<torch::Tensor>& targets, const RenderSettings& settings,
+                     const std::vector<std::string>& names) {
+    const size_t num_test = cameras.size();
+    if (num_test == 0) return {};                                 // metrics.cpp:98-102
+    TORCH_CHECK(targets.size() >= num_test, "evaluate: ", num_test, " cameras but ", targets.size(), " targets");
+    TORCH_CHECK(names.empty() || names.size() >= num_test, "evaluate: fewer image names than cameras");
+    EvalResults results;
+    results.num_gaussians = static_cast<int>(model.positions.size(0));
+    results.sh_degree = settings.active_sh_degree;
+    const auto t_start = std::chrono::steady_clock::now();
+    torch::NoGradGuard no_grad;
+    auto table = torch::empty({static_cast<int64_t>(num_test), 4}, fopt(model.positions));
+    for (size_t v = 0; v < num_test; ++v) {
+        const cugs_camera& cam = cameras[v];
+        auto color = render(model, cam, settings, /*for_backward=*/false).color;
+        torch::Tensor tgt = targets[v];
+        if (tgt.dtype() == torch::kUInt8 && tgt.dim() == 3 && (tgt.size(1) != cam.width || tgt.size(0) != cam.height))
+            tgt = image_to_float(tgt, cam.width, cam.height);     // the reference's resize, metrics.cpp:121-128
+        run_eval(color, tgt, table[static_cast<int64_t>(v)], 11, "evaluate");
+    }
+    const auto rows = table.cpu();                                // the one read-back
+    const float* m = rows.data_ptr<float>();
+    float sum_psnr = 0.0f, sum_ssim = 0.0f;
+    for (size_t v = 0; v < num_test; ++v) {
+        ImageMetrics im;
+        if (!names.empty()) im.image_name = names[v];
+        im.psnr = psnr_from_mse(m[4 * v]);
+        im.ssim = m[4 * v + 1];
+        results.per_image.push_back(im);
+        sum_psnr += im.psnr;                                      // metrics.cpp:143-151
+        sum_ssim += im.ssim;
+    }
+    results.mean_psnr = sum_psnr / static_cast<float>(num_test);
+    results.mean_ssim = sum_ssim / static_cast<float>(num_test);
+    results.eval_time_seconds = std::chrono::duration<float>(std::chrono::steady_clock::now() - t_start).count();
+    return results;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -15,8 +15,10 @@
 
 #include <array>
 #include <string>
+#include <vector>
 
 #include "../../include/cugs_hip.h"
+#include "eval_results.hpp"
 
 namespace cugs_hip {
 
@@ -236,6 +238,24 @@ private:
 // and, if the sizes differ, the reference's resize_image (data/image_io.cpp:35-39, 47-100), bit for bit what
 // trainer.cpp:186-198 builds on the CPU and uploads.
 torch::Tensor image_to_float(const torch::Tensor& view_u8, int width, int height);
+
+// training/metrics.hpp:22-76 over csrc/metrics.hip.  ImageMetrics / EvalResults: eval_results.hpp.
+// eval_metrics: device float[4] = {MSE, mean SSIM, L1 mean, max |rendered - target|}, two launches, no host sync;
+//   `target` is float32 [H,W,3] or the uint8 [H,W,3] of a cached view (expanded in registers); `out` (optional): a
+//   contiguous float32 [4] on the same device to write into - row v of a [V,4] table.  Mean SSIM and the L1 mean are
+//   the bits of combined_loss_and_grad's ssim_mean and l1.
+// compute_psnr / compute_ssim: the reference's scalars (metrics.cpp:21-46; one blocking 16-byte read-back each).
+// evaluate: metrics.cpp:93-163 for `cameras[v]` against `targets[v]` (device tensors: uint8 [h,w,3], resized to the
+//   camera as the reference does when the sizes differ, or float32 [H,W,3]); every view is queued, then ONE
+//   device-to-host copy of the [V,4] table.  `names` (optional) fills ImageMetrics::image_name.
+torch::Tensor eval_metrics(const torch::Tensor& rendered, const torch::Tensor& target, const torch::Tensor& out = {},
+                           int window_size = 11);
+float psnr_from_mse(float mse);
+float compute_psnr(const torch::Tensor& rendered, const torch::Tensor& target);
+float compute_ssim(const torch::Tensor& rendered, const torch::Tensor& target);
+EvalResults evaluate(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                     const std::vector<torch::Tensor>& targets, const RenderSettings& settings,
+                     const std::vector<std::string>& names = {});
 
 // utils/ply_io.hpp:53-64 over csrc/ply.hip: the reference's binary PLY layout, records packed and
 // unpacked on the device.  `optimizer` (optional): the Adam moments and step count ride along as extra properties

@@ -6,6 +6,9 @@
 // calls and link against these symbols.  Default arguments are NOT repeated here: the reference's declarations carry
 // them (projection.hpp:47, projection_backward.hpp:57), a second specification is ill-formed.
 //
+// It also DEFINES cugs::compute_psnr / compute_ssim (training/metrics.hpp:30,39) over csrc/metrics.hip; metrics.cpp
+// drops those two bodies.
+//
 // Compile-checked in this repository against the reference's headers with a stand-in for Eigen
 // (tests/test_reference_glue_compiles.py: -fsyntax-only, then a two-TU link of a declaration-only caller against
 // this file's object); built for real only in the maintainer's tree.
@@ -14,6 +17,7 @@
 #include "core/gaussian_init.hpp"
 #include "core/sh.hpp"
 #include "core/sh_backward.hpp"
+#include "training/metrics.hpp"
 
 #include <type_traits>
 
@@ -145,5 +149,15 @@ GaussianModel init_gaussians_from_sparse(std::span<const SparsePoint> points, in
     model.rotations = m.rotations; model.scales = m.scales;
     return model;
 }
+
+// ---- training/metrics.hpp:30,39:  the two scalars evaluate() (metrics.cpp:134-135) is made of ----
+float compute_psnr(const torch::Tensor& rendered, const torch::Tensor& target) {
+    return cugs_hip::compute_psnr(rendered, target);
+}
+float compute_ssim(const torch::Tensor& rendered, const torch::Tensor& target) {
+    return cugs_hip::compute_ssim(rendered, target);
+}
+static_assert(std::is_same_v<decltype(&compute_psnr), float (*)(const torch::Tensor&, const torch::Tensor&)>);
+static_assert(std::is_same_v<decltype(&compute_ssim), float (*)(const torch::Tensor&, const torch::Tensor&)>);
 
 }  // namespace cugs

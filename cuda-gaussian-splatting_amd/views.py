@@ -95,6 +95,13 @@ class ViewCache:
         """The tensor trainer.cpp:186-198 builds: the view at the camera's resolution, float [H, W, 3]."""
         return image_to_float(self._views[index], width, height)
 
+    def view_u8(self, index: int) -> torch.Tensor:
+        """The cached uint8 [h, w, 3] view itself, for kernels that read 8-bit targets (metrics.eval_metrics)."""
+        return self._views[index]
+
+    def done_reading(self, index: int) -> None:
+        """Counterpart of StreamedViewCache.done_reading; nothing to do for resident views."""
+
 
 class StreamedViewCache:
     """The same targets for view sets that do NOT fit in HBM (SURVEY §8f N4 "decode once, cache, prefetch"): the
@@ -176,18 +183,28 @@ class StreamedViewCache:
         self._slot_view[s], self._slot_ready[s] = index, ev
         self.uploads += 1
 
-    def target(self, index: int, width: int, height: int) -> torch.Tensor:
+    def view_u8(self, index: int) -> torch.Tensor:
+        """The uint8 [h, w, 3] view in its ring slot (uploaded on demand if it was not prefetched); the current stream
+        waits for the upload.  Call done_reading(index) once the kernels that read it are queued: until then the slot
+        is not protected against the next upload."""
         s = self._slot_of(index)
         if s < 0:                                               # not prefetched: upload now, same path
             self.misses += 1
             self.prefetch(index)
             s = self._slot_of(index)
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_event(self._slot_ready[s])
+        torch.cuda.current_stream(self.device).wait_event(self._slot_ready[s])
         src = self._host[index]
-        view = self._slot_buf[s][:src.numel()].view(src.shape)
-        out = image_to_float(view, width, height)
-        free = torch.cuda.Event()
-        free.record(cur)
-        self._slot_free[s] = free
+        return self._slot_buf[s][:src.numel()].view(src.shape)
+
+    def done_reading(self, index: int) -> None:
+        """Everything queued on the current stream so far may read view `index`'s slot; later uploads wait for it."""
+        s = self._slot_of(index)
+        if s >= 0:
+            free = torch.cuda.Event()
+            free.record(torch.cuda.current_stream(self.device))
+            self._slot_free[s] = free
+
+    def target(self, index: int, width: int, height: int) -> torch.Tensor:
+        out = image_to_float(self.view_u8(index), width, height)
+        self.done_reading(index)
         return out

@@ -440,6 +440,22 @@ int cugs_combined_loss(int width, int height, const float* rendered, const float
                        int window_size, void* workspace, size_t workspace_bytes, float* loss_out,
                        float* ssim_map, float* dL_dcolor, void* stream);
 
+/* ---- Evaluation metrics of one view (training/metrics.cpp:21-46: compute_psnr, compute_ssim) ---------------
+ * rendered: [H,W,3] float.  The target is EITHER target_f32 ([H,W,3] float) OR target_u8 ([H,W,3] uint8, a cached
+ * view at the camera's size, expanded in registers as (float)b * (1.0f / 255.0f): the bits of cugs_image_to_float
+ * at equal size followed by the float path); exactly one is non-null.
+ * metrics_out: DEVICE float[4] = {MSE, mean SSIM, mean |x-y|, max |x-y|} (no host sync, no allocation; two
+ * launches, no per-pixel output).  MSE = (float)(sum of (double)d*(double)d / (3 H W)), d = x - y in float; PSNR is
+ * the host's 10 log10(1 / MSE) (metrics.cpp:27-34).  Mean SSIM and the L1 mean are, bit for bit, loss_out[2] and
+ * loss_out[1] of cugs_combined_loss on the same float inputs and window (same per-pixel arithmetic, same
+ * fixed-order fp64 reduction); window_size odd, 3..15, the reference's is 11.  A NaN input gives NaN results.
+ * CUGS_EINVAL for a negative size, an even or out-of-range window, both or neither target, a null pointer or a
+ * workspace shorter than cugs_eval_workspace_bytes with pixels to process; width * height == 0 queues nothing. */
+size_t cugs_eval_workspace_bytes(int width, int height);
+int cugs_eval_metrics(int width, int height, const float* rendered, const float* target_f32,
+                      const uint8_t* target_u8, int window_size, void* workspace, size_t workspace_bytes,
+                      float* metrics_out, void* stream);
+
 /* ---- N2: adaptive density control (optimizer/densification.cpp) ------------------------------
  * cugs_densify_accumulate: DensificationController::accumulate_gradients (densification.cpp:59-88), one
  *   launch, no host sync: for radii > 0, grad_accum += ||dL_dmeans_2d||_2 and grad_count += 1; for every
