@@ -61,6 +61,19 @@ class PoseGrad(C.Structure):
     _fields_ = [("dL_dview", C.c_void_p), ("rows", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_size_t)]
 
+
+class BlendForwardOpts(C.Structure):
+    """struct cugs_blend_forward_opts."""
+    _fields_ = [("zero_buf", C.c_void_p), ("zero_bytes", C.c_size_t), ("tile_order", C.c_void_p),
+                ("depths", C.c_void_p), ("out_depth", C.c_void_p)]
+
+
+class BlendBackwardOpts(C.Structure):
+    """struct cugs_blend_backward_opts."""
+    _fields_ = [("prezeroed", C.c_int), ("abs_grad", C.c_int), ("tile_order", C.c_void_p), ("depths", C.c_void_p),
+                ("dL_ddepth_map", C.c_void_p), ("dL_dalpha", C.c_void_p), ("dL_ddepths", C.c_void_p),
+                ("dL_dmeans_2d_abs", C.c_void_p)]
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -96,24 +109,14 @@ SIGNATURES = {
     "cugs_sort_pairs_predicted_keyed_ordered": (_I, [_L, _L, _P, _P, _P, _P, _I, _I, _P, C.c_size_t, _P, C.c_size_t, _P, _P, _P,
                                                      C.POINTER(C.c_int64), _P, _P]),
     "cugs_tile_order": (_I, [_I, _I, _P, _P, _P]),
-    "cugs_rasterize_forward_ordered": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
-                                            _P, _P, _P, _P, C.c_size_t, _P, _P]),
-    "cugs_rasterize_backward_ordered": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
-                                             _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _P, _P]),
-    "cugs_rasterize_forward_depth": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
-                                          _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
-    "cugs_rasterize_backward_depth": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
-                                           _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
-    "cugs_rasterize_backward_abs": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
-                                         _P, _P, _P, _L, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cugs_rasterize_forward": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                     _P, _P, _P, _P]),
-    "cugs_rasterize_forward_zero": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
-                                         _P, _P, _P, _P, C.c_size_t, _P]),
+    "cugs_rasterize_forward_opts": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
+                                         _P, _P, _P, C.POINTER(BlendForwardOpts), _P]),
     "cugs_rasterize_backward": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
-    "cugs_rasterize_backward_prezeroed": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
-                                               _P, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
+    "cugs_rasterize_backward_opts": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _L, _P, _P, _P, _P, _P, C.POINTER(BlendBackwardOpts), _P]),
     "cugs_project_backward": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F,
                                    _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cugs_project_backward_adam": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,

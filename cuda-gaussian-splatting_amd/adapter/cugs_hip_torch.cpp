@@ -32,6 +32,9 @@ torch::Tensor f32c(const torch::Tensor& t) { return t.contiguous().to(torch::kFl
 template <typename T> T* ptr(const torch::Tensor& t) {
     return (t.defined() && t.numel() > 0) ? t.data_ptr<T>() : nullptr;
 }
+const uint32_t* order_ptr(const torch::Tensor& tile_order) {    // [tiles, 4] int32 records, or undefined
+    return tile_order.defined() ? reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>()) : nullptr;
+}
 torch::TensorOptions fopt(const torch::Tensor& like) { return torch::TensorOptions().dtype(torch::kFloat32).device(like.device()); }
 torch::TensorOptions iopt(const torch::Tensor& like) { return torch::TensorOptions().dtype(torch::kInt32).device(like.device()); }
 
@@ -186,42 +189,19 @@ ForwardOutput rasterize_forward(const torch::Tensor& means_2d, const torch::Tens
     if (tile_order.defined())
         TORCH_CHECK(tile_order.is_contiguous() && tile_order.scalar_type() == torch::kInt32 &&
                     tile_order.numel() == 4 * tr.size(0), "tile_order must be a contiguous [tiles, 4] int32 tensor");
-    if (depths.defined()) {                                     // the depth map too
-        auto z = depths.contiguous().to(torch::kFloat32);
-        check(cugs_rasterize_forward_depth(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
-                                           ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(o.color),
-                                           ptr<float>(o.final_T), ptr<int32_t>(o.n_contrib),
-                                           zero_buf.defined() ? zero_buf.data_ptr() : nullptr,
-                                           zero_buf.defined() ? static_cast<size_t>(zero_buf.numel()) * sizeof(float) : 0,
-                                           tile_order.defined() ? reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>())
-                                                                : nullptr,
-                                           ptr<float>(z), ptr<float>(o.depth_map), stream_of(means_2d)),
-              "cugs_rasterize_forward_depth");
-        return o;
+    const auto z = depths.defined() ? f32c(depths) : depths;    // the depth map too
+    cugs_blend_forward_opts opts{};
+    if (zero_buf.defined()) {                                   // the blend also clears the backward's accumulator
+        opts.zero_buf = zero_buf.data_ptr();
+        opts.zero_bytes = static_cast<size_t>(zero_buf.numel()) * sizeof(float);
     }
-    if (tile_order.defined()) {                                 // workgroups handed out longest tile list first
-        check(cugs_rasterize_forward_ordered(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
-                                             ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(o.color),
-                                             ptr<float>(o.final_T), ptr<int32_t>(o.n_contrib),
-                                             zero_buf.defined() ? zero_buf.data_ptr() : nullptr,
-                                             zero_buf.defined() ? static_cast<size_t>(zero_buf.numel()) * sizeof(float) : 0,
-                                             reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>()),
-                                             stream_of(means_2d)),
-              "cugs_rasterize_forward_ordered");
-        return o;
-    }
-    if (zero_buf.defined()) {
-        check(cugs_rasterize_forward_zero(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
-                                          ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(o.color),
-                                          ptr<float>(o.final_T), ptr<int32_t>(o.n_contrib), zero_buf.data_ptr(),
-                                          static_cast<size_t>(zero_buf.numel()) * sizeof(float), stream_of(means_2d)),
-              "cugs_rasterize_forward_zero");
-        return o;
-    }
-    check(cugs_rasterize_forward(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m), ptr<float>(c),
-                                 ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(o.color),
-                                 ptr<float>(o.final_T), ptr<int32_t>(o.n_contrib), stream_of(means_2d)),
-          "cugs_rasterize_forward");
+    opts.tile_order = order_ptr(tile_order);                    // workgroups handed out longest tile list first
+    opts.depths = ptr<float>(z);
+    opts.out_depth = ptr<float>(o.depth_map);
+    check(cugs_rasterize_forward_opts(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
+                                      ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(o.color),
+                                      ptr<float>(o.final_T), ptr<int32_t>(o.n_contrib), &opts, stream_of(means_2d)),
+          "cugs_rasterize_forward_opts");
     return o;
 }
 
@@ -277,55 +257,23 @@ RasterizeBackwardOutput rasterize_backward(const torch::Tensor& dL_dcolor, const
     if (tile_order.defined())
         TORCH_CHECK(tile_order.is_contiguous() && tile_order.scalar_type() == torch::kInt32 &&
                     tile_order.numel() == 4 * tr.size(0), "tile_order must be a contiguous [tiles, 4] int32 tensor");
-    if (want_abs_grad) {
-        auto f32 = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
-        auto z = f32(depths), dd = f32(dL_ddepth_map), da = f32(dL_dalpha);
-        check(cugs_rasterize_backward_abs(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
-                                          ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g),
-                                          ptr<float>(ft), ptr<int32_t>(nc), n, ptr<float>(o.grad_accum),
-                                          ptr<float>(o.dL_drgb), ptr<float>(o.dL_dopacity_act), ptr<float>(o.dL_dmeans_2d),
-                                          ptr<float>(o.dL_dcov_2d_inv), prezeroed ? 1 : 0,
-                                          tile_order.defined() ? reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>())
-                                                               : nullptr,
-                                          ptr<float>(z), ptr<float>(dd), ptr<float>(da), ptr<float>(o.dL_ddepths),
-                                          unpack ? ptr<float>(o.dL_dmeans_2d_abs) : nullptr, stream_of(dL_dcolor)),
-              "cugs_rasterize_backward_abs");
-        return o;
-    }
-    if (depth_route) {
-        auto z = depths.contiguous().to(torch::kFloat32);
-        auto f32 = [](const torch::Tensor& t) { return t.defined() ? t.contiguous().to(torch::kFloat32) : t; };
-        auto dd = f32(dL_ddepth_map), da = f32(dL_dalpha);
-        check(cugs_rasterize_backward_depth(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
-                                            ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g),
-                                            ptr<float>(ft), ptr<int32_t>(nc), n, ptr<float>(o.grad_accum),
-                                            ptr<float>(o.dL_drgb), ptr<float>(o.dL_dopacity_act), ptr<float>(o.dL_dmeans_2d),
-                                            ptr<float>(o.dL_dcov_2d_inv), prezeroed ? 1 : 0,
-                                            tile_order.defined() ? reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>())
-                                                                 : nullptr,
-                                            ptr<float>(z), ptr<float>(dd), ptr<float>(da), ptr<float>(o.dL_ddepths),
-                                            stream_of(dL_dcolor)),
-              "cugs_rasterize_backward_depth");
-        return o;
-    }
-    if (tile_order.defined()) {
-        check(cugs_rasterize_backward_ordered(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
-                                              ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g),
-                                              ptr<float>(ft), ptr<int32_t>(nc), n, ptr<float>(o.grad_accum),
-                                              ptr<float>(o.dL_drgb), ptr<float>(o.dL_dopacity_act), ptr<float>(o.dL_dmeans_2d),
-                                              ptr<float>(o.dL_dcov_2d_inv), prezeroed ? 1 : 0,
-                                              reinterpret_cast<const uint32_t*>(tile_order.data_ptr<int32_t>()),
-                                              stream_of(dL_dcolor)),
-              "cugs_rasterize_backward_ordered");
-        return o;
-    }
-    auto entry = prezeroed ? cugs_rasterize_backward_prezeroed : cugs_rasterize_backward;
-    check(entry(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m), ptr<float>(c),
-                ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g), ptr<float>(ft),
-                ptr<int32_t>(nc), n, ptr<float>(o.grad_accum), ptr<float>(o.dL_drgb),
-                ptr<float>(o.dL_dopacity_act), ptr<float>(o.dL_dmeans_2d), ptr<float>(o.dL_dcov_2d_inv),
-                stream_of(dL_dcolor)),
-          prezeroed ? "cugs_rasterize_backward_prezeroed" : "cugs_rasterize_backward");
+    auto f32 = [](const torch::Tensor& t) { return t.defined() ? f32c(t) : t; };
+    const auto z = f32(depths), dd = f32(dL_ddepth_map), da = f32(dL_dalpha);
+    cugs_blend_backward_opts opts{};
+    opts.prezeroed = prezeroed ? 1 : 0;
+    opts.abs_grad = want_abs_grad ? 1 : 0;
+    opts.tile_order = order_ptr(tile_order);
+    opts.depths = ptr<float>(z);
+    opts.dL_ddepth_map = ptr<float>(dd);
+    opts.dL_dalpha = ptr<float>(da);
+    opts.dL_ddepths = ptr<float>(o.dL_ddepths);
+    opts.dL_dmeans_2d_abs = unpack ? ptr<float>(o.dL_dmeans_2d_abs) : nullptr;   // not unpacked: the rows' own words
+    check(cugs_rasterize_backward_opts(img_w, img_h, background, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m),
+                                       ptr<float>(c), ptr<float>(r), ptr<float>(op), ptr<float>(packed), ptr<float>(g),
+                                       ptr<float>(ft), ptr<int32_t>(nc), n, ptr<float>(o.grad_accum),
+                                       ptr<float>(o.dL_drgb), ptr<float>(o.dL_dopacity_act), ptr<float>(o.dL_dmeans_2d),
+                                       ptr<float>(o.dL_dcov_2d_inv), &opts, stream_of(dL_dcolor)),
+          "cugs_rasterize_backward_opts");
     return o;
 }
 

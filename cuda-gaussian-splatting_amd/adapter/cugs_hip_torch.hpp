@@ -111,7 +111,7 @@ torch::Tensor evaluate_sh_backward_cuda(int degree, const torch::Tensor& sh_coef
                                         const torch::Tensor& dL_dcolor);
 
 // `for_backward` = false (evaluation, viewer; not in the reference): no accumulator is prepared for a backward pass.
-// `want_depth_map` (not in the reference): also RenderOutput::depth_map (cugs_rasterize_forward_depth); the colour
+// `want_depth_map` (not in the reference): also RenderOutput::depth_map (cugs_blend_forward_opts::out_depth); the colour
 // outputs are unchanged, bit for bit.
 RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
                     bool for_backward = true, bool want_depth_map = false);
@@ -134,7 +134,7 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
 // camera.view (row 3 zero; the SH view direction held constant), on every route above, with no host sync; every other
 // output is unchanged, bit for bit.
 // `want_abs_grad` (not in the reference): BackwardOutput::dL_dmeans_2d_abs, the AbsGrad densification
-// signal, from the backward blend (cugs_rasterize_backward_abs), on every route above; every other output is the same
+// signal, from the backward blend (cugs_blend_backward_opts::abs_grad), on every route above; every other output is the same
 // up to the order of the blend's atomic adds.
 
 // training/loss.hpp:21-52 + the autograd step of trainer.cpp:214-217 in two launches.

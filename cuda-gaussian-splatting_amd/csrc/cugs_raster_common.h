@@ -17,6 +17,8 @@
 
 #include "cugs_gaussian_math.h"
 
+#include <type_traits>
+
 #define CUGS_REC_F4 3      // float4s per LDS record (CUGS_PACKED_STRIDE / 4)
 
 struct RasterGeom {
@@ -35,6 +37,14 @@ struct RasterSrc {
     const uint4* tile_order;    // may be NULL -> the spatial order of cugs_blend_tile; else workgroup b works on record b:
                                 // {tile, first pair, one past the last pair, 0} - tile and range in ONE load (cugs_tile_order)
 };
+
+// Host side, kernel selection: f(std::true_type{}) or f(std::false_type{}) - a run-time flag becomes the template
+// argument P() inside f.  Nest one call per flag.
+template <typename F>
+static inline void cugs_with_bool(bool flag, F&& f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // Stage list entry `li` (if < end) into LDS slot threadIdx.x.  The LDS copy of the record carries the
 // Gaussian index (as bits) in its spare word 7, so that the backward's scatter address comes

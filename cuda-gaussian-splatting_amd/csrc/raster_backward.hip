@@ -28,12 +28,12 @@
 //     (k_project_backward / k_unpack_grads).  Accumulator row: {drgb[3], dopa, M1x, M1y, M2xx, M2xy, M2yy};
 //   * T *= rcp(1 - al) needs no "did it contribute" select: v_rcp_f32(1.0f) is exactly 1.0f
 //     (tests/test_gpu_reduce9.py checks it on the device).
-// DEPTH (cugs_rasterize_backward_depth): the depth map is a colour channel with c = z (record word 9)
+// DEPTH (the depth route of cugs_blend_backward_opts): the depth map is a colour channel with c = z (record word 9)
 // and background 0, the alpha map 1 - final_T one with c = 1 and background 0.  dL/dD joins the per-step dot product
 // (G += dL/dD z: one FMA) and phase 2 forms a TENTH sum, sum weight * dL/dD = dL/dz, delivered to word 9 of the row by
 // reduce10r16.  dL/dA needs no per-step work: sum_i alpha_i T_i + final_T = 1, so the channel (c = 1, bg = 0) has the
 // gradient of (c = 0, bg = -1), which only enters D's starting value (D -= final_T dL/dA).
-// ABS (cugs_rasterize_backward_abs): the AbsGrad densification signal.  Phase 2 also forms, per
+// ABS (cugs_blend_backward_opts::abs_grad): the AbsGrad densification signal.  Phase 2 also forms, per
 // Gaussian, sum |dL/dpower (a dx + b dy)| and sum |dL/dpower (b dx + c dy)| over the pixels - the per-pixel summands of
 // dL/dmean2d with fabs around each - and reduce12ar16 delivers them to words 10 and 11 of the row.  Phase 1 is unchanged.
 // The summation order differs from any sequential order; the oracle accumulates in fp64.
@@ -387,19 +387,17 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_unpack_grads(int64_t n, const fl
 
 }  // namespace
 
-namespace {
-int rasterize_backward_impl(int width, int height, const float background_host[3],
-                                       const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                       const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                       const float* opacities_act, const float* packed,
-                                       const float* dL_dcolor, const float* final_T,
-                                       const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                       float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                       float* dL_dcov_2d_inv, bool prezeroed, const uint32_t* tile_order, void* stream,
-                                       bool depth_map = false, const float* depths = nullptr,
-                                       const float* dL_ddepth_map = nullptr, const float* dL_dalpha = nullptr,
-                                       float* dL_ddepths = nullptr, bool abs_grad = false,
-                                       float* dL_dmeans_2d_abs = nullptr) {
+extern "C" int cugs_rasterize_backward_opts(int width, int height, const float background_host[3],
+                                            const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                            const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                            const float* opacities_act, const float* packed,
+                                            const float* dL_dcolor, const float* final_T,
+                                            const int32_t* n_contrib, int64_t n, float* grad_accum,
+                                            float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                            float* dL_dcov_2d_inv, const cugs_blend_backward_opts* opts, void* stream) {
+    const cugs_blend_backward_opts o = opts ? *opts : cugs_blend_backward_opts{};
+    const bool depth_map = o.depths || o.dL_ddepth_map || o.dL_dalpha;    // all NULL: the colour-only kernels
+    const bool abs_grad = o.abs_grad != 0;
     if (width < 0 || height < 0 || n < 0 || !background_host) return CUGS_EINVAL;
     if (n == 0) return 0;
     if (!grad_accum) return CUGS_EINVAL;
@@ -407,104 +405,63 @@ int rasterize_backward_impl(int width, int height, const float background_host[3
     const int n_soa = (dL_drgb != nullptr) + (dL_dopacity_act != nullptr) + (dL_dmeans_2d != nullptr) +
                       (dL_dcov_2d_inv != nullptr);
     if (n_soa != 0 && n_soa != 4) return CUGS_EINVAL;
-    if (depth_map && (n_soa == 4) != (dL_ddepths != nullptr)) return CUGS_EINVAL;   // dL_ddepths with the four, not alone
-    if (!depth_map && dL_ddepths) return CUGS_EINVAL;                               // ... and on the depth route only
-    if (abs_grad && (n_soa == 4) != (dL_dmeans_2d_abs != nullptr)) return CUGS_EINVAL;   // the same for the absolute tensor
+    if (depth_map && (n_soa == 4) != (o.dL_ddepths != nullptr)) return CUGS_EINVAL;   // dL_ddepths with the four, not alone
+    if (!depth_map && o.dL_ddepths) return CUGS_EINVAL;                               // ... and on the depth route only
+    if (abs_grad && (n_soa == 4) != (o.dL_dmeans_2d_abs != nullptr)) return CUGS_EINVAL;   // the same for the absolute tensor
     if (n_soa == 4 && !packed && !cov_2d_inv) return CUGS_EINVAL;
     if (packed && !cugs_aligned16(packed)) return CUGS_EALIGN;
-    if (tile_order && !cugs_aligned16(tile_order)) return CUGS_EALIGN;
+    if (o.tile_order && !cugs_aligned16(o.tile_order)) return CUGS_EALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int64_t rows = n;
 #ifdef CUGS_DEV
     const bool stats = cugs_dev_backward_stats();          // the caller allocated n + 1 rows (tools/ablate_backward.py)
     if (stats) rows = n + 1;
 #endif
-    if (!prezeroed || rows != n)
+    if (!o.prezeroed || rows != n)
         CUGS_RETURN_IF_HIP(hipMemsetAsync(grad_accum, 0, sizeof(float) * CUGS_GRAD_STRIDE * (size_t)rows, st));
 
     const int ntx = (width + CUGS_TILE - 1) / CUGS_TILE, nty = (height + CUGS_TILE - 1) / CUGS_TILE;
     if (ntx > 0 && nty > 0 && gaussian_indices) {               // backward.cu:267-269; NULL indices = no pairs
         if (!tile_ranges || !dL_dcolor || !final_T || !n_contrib) return CUGS_EINVAL;
         if (!packed && (!means_2d || !cov_2d_inv || !rgb || !opacities_act)) return CUGS_EINVAL;
-        if (depth_map && !depths) return CUGS_EINVAL;
+        if (depth_map && !o.depths) return CUGS_EINVAL;
         if ((int64_t)width * height > 2147483647ll / 3) return CUGS_EOVERFLOW;
         RasterGeom geo{width, height, ntx, ntx * nty, background_host[0], background_host[1], background_host[2]};
-        RasterSrc src{tile_ranges, gaussian_indices, packed, means_2d, cov_2d_inv, rgb, opacities_act, reinterpret_cast<const uint4*>(tile_order)};
+        RasterSrc src{tile_ranges, gaussian_indices, packed, means_2d, cov_2d_inv, rgb, opacities_act, reinterpret_cast<const uint4*>(o.tile_order)};
         const bool wide = rows > (int64_t(1) << 26);            // 64-byte rows beyond a 32-bit byte offset
         int64_t stats_arg = n;                                  // STATS builds: the row that takes the counters
 #ifdef CUGS_DEV
         if (const char* e = std::getenv("CUGS_BWD_NO_ATOMICS")) if (e[0] == '1') stats_arg = -2;
 #endif
-#define CUGS_LAUNCH_BWD(P, W, S)                                                                              \
-    hipLaunchKernelGGL((k_raster_backward<P, W, S>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, \
-                       dL_dcolor, final_T, n_contrib, grad_accum, stats_arg, nullptr, nullptr, nullptr)
-#define CUGS_LAUNCH_BWD_DEPTH(P, W)                                                                                  \
-    hipLaunchKernelGGL((k_raster_backward<P, W, false, true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, \
-                       dL_dcolor, final_T, n_contrib, grad_accum, stats_arg, depths, dL_ddepth_map, dL_dalpha)
-#define CUGS_LAUNCH_BWD_ABS(P, W, D)                                                                              \
-    hipLaunchKernelGGL((k_raster_backward<P, W, false, D, true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, \
-                       dL_dcolor, final_T, n_contrib, grad_accum, stats_arg, depths, dL_ddepth_map, dL_dalpha)
-        if (abs_grad) {                                         // no step counters on these routes either
-            if (depth_map) {
-                if (packed) {
-                    if (wide) CUGS_LAUNCH_BWD_ABS(true, true, true); else CUGS_LAUNCH_BWD_ABS(true, false, true);
-                } else {
-                    if (wide) CUGS_LAUNCH_BWD_ABS(false, true, true); else CUGS_LAUNCH_BWD_ABS(false, false, true);
-                }
-            } else if (packed) {
-                if (wide) CUGS_LAUNCH_BWD_ABS(true, true, false); else CUGS_LAUNCH_BWD_ABS(true, false, false);
-            } else {
-                if (wide) CUGS_LAUNCH_BWD_ABS(false, true, false); else CUGS_LAUNCH_BWD_ABS(false, false, false);
-            }
-        } else if (depth_map) {                                 // no step counters on this route
-            if (packed) {
-                if (wide) CUGS_LAUNCH_BWD_DEPTH(true, true); else CUGS_LAUNCH_BWD_DEPTH(true, false);
-            } else {
-                if (wide) CUGS_LAUNCH_BWD_DEPTH(false, true); else CUGS_LAUNCH_BWD_DEPTH(false, false);
-            }
-        } else
+        const auto launch = [&](auto* kernel) {
+            hipLaunchKernelGGL(kernel, dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src, dL_dcolor, final_T, n_contrib,
+                               grad_accum, stats_arg, o.depths, o.dL_ddepth_map, o.dL_dalpha);
+        };
 #ifdef CUGS_DEV
-        if (stats) {
-            if (packed) CUGS_LAUNCH_BWD(true, true, true); else CUGS_LAUNCH_BWD(false, true, true);
-        } else
+        if (stats && !depth_map && !abs_grad)                   // no step counters on the DEPTH and ABS routes
+            cugs_with_bool(packed != nullptr, [&](auto P) { launch(k_raster_backward<P(), true, true>); });
+        else
 #endif
-        if (packed) {
-            if (wide) CUGS_LAUNCH_BWD(true, true, false); else CUGS_LAUNCH_BWD(true, false, false);
-        } else {
-            if (wide) CUGS_LAUNCH_BWD(false, true, false); else CUGS_LAUNCH_BWD(false, false, false);
-        }
-#undef CUGS_LAUNCH_BWD
-#undef CUGS_LAUNCH_BWD_DEPTH
-#undef CUGS_LAUNCH_BWD_ABS
+        cugs_with_bool(packed != nullptr, [&](auto P) { cugs_with_bool(wide, [&](auto W) {
+            cugs_with_bool(depth_map, [&](auto D) { cugs_with_bool(abs_grad, [&](auto A) {
+                launch(k_raster_backward<P(), W(), false, D(), A()>);
+            }); });
+        }); });
         CUGS_LAUNCH_CHECK();
     }
     if (n_soa == 4) {
         const dim3 grid((unsigned)((n + CUGS_BLOCK - 1) / CUGS_BLOCK));
-#define CUGS_LAUNCH_UNPACK(P, D)                                                                                 \
-    hipLaunchKernelGGL((k_unpack_grads<P, D>), grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed, cov_2d_inv, \
-                       dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, dL_ddepths, nullptr)
-#define CUGS_LAUNCH_UNPACK_ABS(P, D)                                                                                   \
-    hipLaunchKernelGGL((k_unpack_grads<P, D, true>), grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed, cov_2d_inv, \
-                       dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, dL_ddepths, dL_dmeans_2d_abs)
-        if (abs_grad) {
-            if (depth_map) {
-                if (packed) CUGS_LAUNCH_UNPACK_ABS(true, true); else CUGS_LAUNCH_UNPACK_ABS(false, true);
-            } else {
-                if (packed) CUGS_LAUNCH_UNPACK_ABS(true, false); else CUGS_LAUNCH_UNPACK_ABS(false, false);
-            }
-        } else if (depth_map) {
-            if (packed) CUGS_LAUNCH_UNPACK(true, true); else CUGS_LAUNCH_UNPACK(false, true);
-        } else {
-            if (packed) CUGS_LAUNCH_UNPACK(true, false); else CUGS_LAUNCH_UNPACK(false, false);
-        }
-#undef CUGS_LAUNCH_UNPACK
-#undef CUGS_LAUNCH_UNPACK_ABS
+        cugs_with_bool(packed != nullptr, [&](auto P) { cugs_with_bool(depth_map, [&](auto D) {
+            cugs_with_bool(abs_grad, [&](auto A) {
+                hipLaunchKernelGGL((k_unpack_grads<P(), D(), A()>), grid, dim3(CUGS_BLOCK), 0, st, n, grad_accum, packed,
+                                   cov_2d_inv, dL_drgb, dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, o.dL_ddepths,
+                                   o.dL_dmeans_2d_abs);
+            });
+        }); });
         CUGS_LAUNCH_CHECK();
     }
     return 0;
 }
-
-}  // namespace
 
 extern "C" int cugs_rasterize_backward(int width, int height, const float background_host[3],
                                        const int32_t* tile_ranges, const int32_t* gaussian_indices,
@@ -514,69 +471,9 @@ extern "C" int cugs_rasterize_backward(int width, int height, const float backgr
                                        const int32_t* n_contrib, int64_t n, float* grad_accum,
                                        float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
                                        float* dL_dcov_2d_inv, void* stream) {
-    return rasterize_backward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                   opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
-                                   dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, false, nullptr, stream);
-}
-
-extern "C" int cugs_rasterize_backward_prezeroed(int width, int height, const float background_host[3],
-                                                 const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                                 const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                                 const float* opacities_act, const float* packed,
-                                                 const float* dL_dcolor, const float* final_T,
-                                                 const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                                 float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                                 float* dL_dcov_2d_inv, void* stream) {
-    return rasterize_backward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                   opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
-                                   dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, true, nullptr, stream);
-}
-
-extern "C" int cugs_rasterize_backward_ordered(int width, int height, const float background_host[3],
-                                               const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                               const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                               const float* opacities_act, const float* packed,
-                                               const float* dL_dcolor, const float* final_T,
-                                               const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                               float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                               float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
-                                               void* stream) {
-    return rasterize_backward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                   opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
-                                   dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, prezeroed != 0, tile_order, stream);
-}
-
-extern "C" int cugs_rasterize_backward_depth(int width, int height, const float background_host[3],
-                                             const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                             const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                             const float* opacities_act, const float* packed,
-                                             const float* dL_dcolor, const float* final_T,
-                                             const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                             float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                             float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
-                                             const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
-                                             float* dL_ddepths, void* stream) {
-    return rasterize_backward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                   opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
-                                   dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, prezeroed != 0, tile_order, stream, true,
-                                   depths, dL_ddepth_map, dL_dalpha, dL_ddepths);
-}
-
-extern "C" int cugs_rasterize_backward_abs(int width, int height, const float background_host[3],
-                                           const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                           const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                           const float* opacities_act, const float* packed,
-                                           const float* dL_dcolor, const float* final_T,
-                                           const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                           float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                           float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
-                                           const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
-                                           float* dL_ddepths, float* dL_dmeans_2d_abs, void* stream) {
-    const bool depth_map = depths || dL_ddepth_map || dL_dalpha;          // all NULL: the colour-only ABS kernel
-    return rasterize_backward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                   opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
-                                   dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, prezeroed != 0, tile_order, stream,
-                                   depth_map, depths, dL_ddepth_map, dL_dalpha, dL_ddepths, true, dL_dmeans_2d_abs);
+    return cugs_rasterize_backward_opts(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv,
+                                        rgb, opacities_act, packed, dL_dcolor, final_T, n_contrib, n, grad_accum, dL_drgb,
+                                        dL_dopacity_act, dL_dmeans_2d, dL_dcov_2d_inv, nullptr, stream);
 }
 
 #ifdef CUGS_DEV

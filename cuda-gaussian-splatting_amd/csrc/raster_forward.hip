@@ -11,7 +11,7 @@
 // (~35 instructions per surviving (pixel, Gaussian) evaluation); HBM traffic is the 4 B index +
 // 48 B record per (tile, Gaussian) pair plus 20 B per pixel written.
 //
-// DEPTH (cugs_rasterize_forward_depth): the accumulated depth map D = sum_i z_i alpha_i T_i is one more
+// DEPTH (cugs_blend_forward_opts::out_depth): the accumulated depth map D = sum_i z_i alpha_i T_i is one more
 // colour channel with value z_i = depths[i] and background 0.  stage_record puts z into word 9 of the LDS record (0 in
 // the colour instantiations), so red and depth are the aligned pair (r, z) and accumulate in ONE v_pk_fma_f32, as green
 // and blue do: no extra VALU per step, and each lane's IEEE fma gives the bits of fmaf - the depth map is bit for bit
@@ -29,7 +29,7 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
     __shared__ float4 s_rec[CUGS_BLOCK * CUGS_REC_F4];
     __shared__ int s_wave_done[4];
 
-    // Housekeeping for the backward (cugs_rasterize_forward_zero): this kernel is bound by instruction issue and
+    // Housekeeping for the backward (cugs_blend_forward_opts::zero_buf): this kernel is bound by instruction issue and
     // leaves HBM nearly idle, so each workgroup clears its slice of the gradient accumulator here - the 64 B/Gaussian
     // fill that otherwise runs by itself in front of the backward blend.
     if (zero_buf) {
@@ -38,7 +38,6 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
         for (uint32_t e = lo + threadIdx.x; e < hi; e += CUGS_BLOCK) cugs_stnt(zero_buf + e, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     }
 
-    // heaviest tile first when the caller brings an order (cugs_tile_order: kernel-uniform), else the spatial order
     // heaviest tile first when the caller brings an order (cugs_tile_order: kernel-uniform), else the spatial order
     unsigned tile;
     int range_start, range_end;
@@ -166,92 +165,53 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_raster_forward_depth(RasterGeom 
 
 }  // namespace
 
-namespace {
-int rasterize_forward_impl(int width, int height, const float background_host[3], const int32_t* tile_ranges,
-                           const int32_t* gaussian_indices, const float* means_2d, const float* cov_2d_inv,
-                           const float* rgb, const float* opacities_act, const float* packed, float* out_color,
-                           float* out_final_T, int32_t* out_n_contrib, void* zero_buf, size_t zero_bytes,
-                           const uint32_t* tile_order, void* stream, bool depth_map = false,
-                           const float* depths = nullptr, float* out_depth = nullptr) {
+extern "C" int cugs_rasterize_forward_opts(int width, int height, const float background_host[3],
+                                           const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                           const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                           const float* opacities_act, const float* packed, float* out_color,
+                                           float* out_final_T, int32_t* out_n_contrib,
+                                           const cugs_blend_forward_opts* opts, void* stream) {
+    const cugs_blend_forward_opts o = opts ? *opts : cugs_blend_forward_opts{};
+    const bool depth_map = o.depths || o.out_depth;
     if (width < 0 || height < 0 || !background_host) return CUGS_EINVAL;
-    if (zero_bytes && (!zero_buf || (reinterpret_cast<uintptr_t>(zero_buf) & 15u) || (zero_bytes & 15u) ||
-                       zero_bytes / 16 > 0xFFFFFFFFull))
-        return zero_buf ? CUGS_EALIGN : CUGS_EINVAL;
+    if (o.zero_bytes && (!o.zero_buf || (reinterpret_cast<uintptr_t>(o.zero_buf) & 15u) || (o.zero_bytes & 15u) ||
+                       o.zero_bytes / 16 > 0xFFFFFFFFull))
+        return o.zero_buf ? CUGS_EALIGN : CUGS_EINVAL;
     const int ntx = (width + CUGS_TILE - 1) / CUGS_TILE, nty = (height + CUGS_TILE - 1) / CUGS_TILE;
     if (ntx == 0 || nty == 0) {                               // forward.cu:204-210: nothing to draw
-        if (zero_bytes) CUGS_RETURN_IF_HIP(hipMemsetAsync(zero_buf, 0, zero_bytes, static_cast<hipStream_t>(stream)));
+        if (o.zero_bytes) CUGS_RETURN_IF_HIP(hipMemsetAsync(o.zero_buf, 0, o.zero_bytes, static_cast<hipStream_t>(stream)));
         return 0;
     }
     if (!tile_ranges || !out_color || !out_final_T || !out_n_contrib) return CUGS_EINVAL;
-    if (depth_map && (!out_depth || (gaussian_indices && !depths))) return CUGS_EINVAL;
+    if (depth_map && (!o.out_depth || (gaussian_indices && !o.depths))) return CUGS_EINVAL;
     // gaussian_indices and the per-Gaussian sources may be NULL for an empty pair list (P == 0: every
     // tile range is {0,0} and nothing is dereferenced).  With indices present a source is required.
     if (gaussian_indices && !packed && (!means_2d || !cov_2d_inv || !rgb || !opacities_act)) return CUGS_EINVAL;
     if (packed && !cugs_aligned16(packed)) return CUGS_EALIGN;
-    if (tile_order && !cugs_aligned16(tile_order)) return CUGS_EALIGN;
+    if (o.tile_order && !cugs_aligned16(o.tile_order)) return CUGS_EALIGN;
     if ((int64_t)width * height > 2147483647ll / 3) return CUGS_EOVERFLOW;
     RasterGeom geo{width, height, ntx, ntx * nty, background_host[0], background_host[1], background_host[2]};
-    RasterSrc src{tile_ranges, gaussian_indices, packed, means_2d, cov_2d_inv, rgb, opacities_act, reinterpret_cast<const uint4*>(tile_order)};
+    RasterSrc src{tile_ranges, gaussian_indices, packed, means_2d, cov_2d_inv, rgb, opacities_act, reinterpret_cast<const uint4*>(o.tile_order)};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float4* zb = zero_bytes ? static_cast<float4*>(zero_buf) : nullptr;
-    const uint32_t zv = (uint32_t)(zero_bytes / 16);
-    if (depth_map) {
-        if (packed)
-            hipLaunchKernelGGL((k_raster_forward_depth<true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
-                               out_color, out_final_T, out_n_contrib, zb, zv, depths, out_depth);
+    float4* zb = o.zero_bytes ? static_cast<float4*>(o.zero_buf) : nullptr;
+    const uint32_t zv = (uint32_t)(o.zero_bytes / 16);
+    cugs_with_bool(packed != nullptr, [&](auto P) {
+        if (depth_map)
+            hipLaunchKernelGGL((k_raster_forward_depth<P()>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
+                               out_color, out_final_T, out_n_contrib, zb, zv, o.depths, o.out_depth);
         else
-            hipLaunchKernelGGL((k_raster_forward_depth<false>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
-                               out_color, out_final_T, out_n_contrib, zb, zv, depths, out_depth);
-    } else if (packed) {
-        hipLaunchKernelGGL((k_raster_forward<true>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
-                           out_color, out_final_T, out_n_contrib, zb, zv);
-    } else {
-        hipLaunchKernelGGL((k_raster_forward<false>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
-                           out_color, out_final_T, out_n_contrib, zb, zv);
-    }
+            hipLaunchKernelGGL((k_raster_forward<P()>), dim3(geo.ntiles), dim3(CUGS_BLOCK), 0, st, geo, src,
+                               out_color, out_final_T, out_n_contrib, zb, zv);
+    });
     CUGS_LAUNCH_CHECK();
     return 0;
 }
-}  // namespace
 
 extern "C" int cugs_rasterize_forward(int width, int height, const float background_host[3],
                                       const int32_t* tile_ranges, const int32_t* gaussian_indices,
                                       const float* means_2d, const float* cov_2d_inv, const float* rgb,
                                       const float* opacities_act, const float* packed, float* out_color,
                                       float* out_final_T, int32_t* out_n_contrib, void* stream) {
-    return rasterize_forward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                  opacities_act, packed, out_color, out_final_T, out_n_contrib, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int cugs_rasterize_forward_zero(int width, int height, const float background_host[3],
-                                           const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                           const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                           const float* opacities_act, const float* packed, float* out_color,
-                                           float* out_final_T, int32_t* out_n_contrib, void* zero_buf,
-                                           size_t zero_bytes, void* stream) {
-    return rasterize_forward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                  opacities_act, packed, out_color, out_final_T, out_n_contrib, zero_buf, zero_bytes, nullptr, stream);
-}
-
-extern "C" int cugs_rasterize_forward_ordered(int width, int height, const float background_host[3],
-                                              const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                              const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                              const float* opacities_act, const float* packed, float* out_color,
-                                              float* out_final_T, int32_t* out_n_contrib, void* zero_buf,
-                                              size_t zero_bytes, const uint32_t* tile_order, void* stream) {
-    return rasterize_forward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                  opacities_act, packed, out_color, out_final_T, out_n_contrib, zero_buf, zero_bytes, tile_order,
-                                  stream);
-}
-
-extern "C" int cugs_rasterize_forward_depth(int width, int height, const float background_host[3],
-                                            const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                            const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                            const float* opacities_act, const float* packed, float* out_color,
-                                            float* out_final_T, int32_t* out_n_contrib, void* zero_buf,
-                                            size_t zero_bytes, const uint32_t* tile_order, const float* depths,
-                                            float* out_depth, void* stream) {
-    return rasterize_forward_impl(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv, rgb,
-                                  opacities_act, packed, out_color, out_final_T, out_n_contrib, zero_buf, zero_bytes, tile_order,
-                                  stream, true, depths, out_depth);
+    return cugs_rasterize_forward_opts(width, height, background_host, tile_ranges, gaussian_indices, means_2d, cov_2d_inv,
+                                       rgb, opacities_act, packed, out_color, out_final_T, out_n_contrib, nullptr, stream);
 }

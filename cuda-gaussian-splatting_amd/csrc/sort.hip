@@ -424,7 +424,7 @@ extern "C" int cugs_sort_pairs_predicted_keyed(int64_t n, int64_t capacity, cons
 }
 
 // cugs_sort_pairs_predicted_keyed that also leaves, in tile_order[tiles][4], the tiles ordered by the length of their lists,
-// longest first ({tile, first pair, one past the last pair, 0} each): what cugs_rasterize_forward_ordered / cugs_rasterize_backward_ordered hand their workgroups out by.
+// longest first ({tile, first pair, one past the last pair, 0} each): what the blends hand their workgroups out by (`tile_order` in their options).
 extern "C" int cugs_sort_pairs_predicted_keyed_ordered(int64_t n, int64_t capacity, const float* means_2d, const float* depths,
                                                        const int32_t* radii, const int32_t* tiles_touched, int width,
                                                        int height, void* workspace, size_t workspace_bytes,

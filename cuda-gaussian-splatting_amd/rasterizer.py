@@ -439,11 +439,11 @@ def rasterize_forward(means_2d: torch.Tensor, cov_2d_inv: torch.Tensor, rgb: tor
                       tile_order: Optional[torch.Tensor] = None,
                       depths: Optional[torch.Tensor] = None) -> ForwardOutput:
     """`zero_buf` (optional, not in the reference): a contiguous float32 tensor the launch also fills with zeros -
-    the accumulator of the backward blend, cleared for free by this issue-bound kernel (cugs_rasterize_forward_zero).
+    the accumulator of the backward blend, cleared for free by this issue-bound kernel (cugs_blend_forward_opts::zero_buf).
     `tile_order` (optional, not in the reference): [tiles, 4] int32, the order the workgroups take the tiles in
     (tile_order_of / SortingOutput.tile_order: longest list first); the outputs do not depend on it.
     `depths` (optional, not in the reference): the [N] depths of the projection - the blend also accumulates the depth
-    map sum_i z_i alpha_i T_i into ForwardOutput.depth_map (cugs_rasterize_forward_depth); colour, final_T and n_contrib
+    map sum_i z_i alpha_i T_i into ForwardOutput.depth_map (cugs_blend_forward_opts::out_depth); colour, final_T and n_contrib
     are unchanged, bit for bit."""
     _torch_check(means_2d.is_cuda, "means_2d must be on CUDA")
     dev = means_2d.device
@@ -466,39 +466,15 @@ def rasterize_forward(means_2d: torch.Tensor, cov_2d_inv: torch.Tensor, rgb: tor
     if tile_order is not None:
         _torch_check(tile_order.is_contiguous() and tile_order.dtype == torch.int32 and
                      tile_order.numel() == 4 * tile_ranges.shape[0], "tile_order must be a contiguous [tiles, 4] int32 tensor")
-    if depths is not None:
-        check(lib.cugs_rasterize_forward_depth(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                               _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                               _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                               _ptr(opacities.contiguous()), _ptr(packed), _ptr(color), _ptr(final_T),
-                                               _ptr(n_contrib), _ptr(zero_buf),
-                                               zero_buf.numel() * 4 if zero_buf is not None else 0, _ptr(tile_order),
-                                               _ptr(_f32c(depths)), _ptr(depth_map), _stream(dev)),
-              "cugs_rasterize_forward_depth")
-        return ForwardOutput(color, final_T, n_contrib, depth_map)
-    if tile_order is not None:
-        check(lib.cugs_rasterize_forward_ordered(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                                 _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                                 _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                                 _ptr(opacities.contiguous()), _ptr(packed), _ptr(color), _ptr(final_T),
-                                                 _ptr(n_contrib), _ptr(zero_buf),
-                                                 zero_buf.numel() * 4 if zero_buf is not None else 0, _ptr(tile_order),
-                                                 _stream(dev)), "cugs_rasterize_forward_ordered")
-        return ForwardOutput(color, final_T, n_contrib)
-    if zero_buf is not None:
-        check(lib.cugs_rasterize_forward_zero(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                              _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                              _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                              _ptr(opacities.contiguous()), _ptr(packed), _ptr(color), _ptr(final_T),
-                                              _ptr(n_contrib), _ptr(zero_buf), zero_buf.numel() * 4, _stream(dev)),
-              "cugs_rasterize_forward_zero")
-        return ForwardOutput(color, final_T, n_contrib)
-    check(lib.cugs_rasterize_forward(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                     _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                     _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                     _ptr(opacities.contiguous()), _ptr(packed), _ptr(color), _ptr(final_T),
-                                     _ptr(n_contrib), _stream(dev)), "cugs_rasterize_forward")
-    return ForwardOutput(color, final_T, n_contrib)
+    z = None if depths is None else _f32c(depths)
+    opts = _lib.BlendForwardOpts(_ptr(zero_buf), zero_buf.numel() * 4 if zero_buf is not None else 0, _ptr(tile_order),
+                                 _ptr(z), _ptr(depth_map))
+    check(lib.cugs_rasterize_forward_opts(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
+                                          _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
+                                          _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
+                                          _ptr(opacities.contiguous()), _ptr(packed), _ptr(color), _ptr(final_T),
+                                          _ptr(n_contrib), C.byref(opts), _stream(dev)), "cugs_rasterize_forward_opts")
+    return ForwardOutput(color, final_T, n_contrib, depth_map)
 
 
 def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_inv: torch.Tensor,
@@ -517,10 +493,10 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
     the atomic adds.
     `depths`, `dL_ddepth_map`, `dL_dalpha` (optional, not in the reference): the gradients of the depth map
     (rasterize_forward(..., depths=...)) and of the alpha map 1 - final_T, [H,W] each, either may be None (zero);
-    `depths` is required with either (cugs_rasterize_backward_depth).  They add to the opacity and 2-D gradients; dL/dz
+    `depths` is required with either (the depth route of cugs_blend_backward_opts).  They add to the opacity and 2-D gradients; dL/dz
     goes to word 9 of each accumulator row and, unpacked, to RasterizeBackwardOutput.dL_ddepths.
     `want_abs_grad=True` (not in the reference): the blend also sums the ABSOLUTE value of every
-    per-pixel 2-D mean gradient (AbsGS / `absgrad`) into words 10 and 11 of each row (cugs_rasterize_backward_abs), with
+    per-pixel 2-D mean gradient (AbsGS / `absgrad`) into words 10 and 11 of each row (cugs_blend_backward_opts::abs_grad), with
     or without the depth arguments.  RasterizeBackwardOutput.dL_dmeans_2d_abs is [N,2]: its own tensor when unpacked,
     the [:, 10:12] view of grad_accum with unpack=False.  Every other output is the same up to the order of the atomic
     adds."""
@@ -541,7 +517,6 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
         _torch_check(tuple(zeroed_accum.shape) == (n, _lib.GRAD_STRIDE) and zeroed_accum.is_contiguous(),
                      "zeroed_accum must be a contiguous [N, 16] float32 tensor")
     accum = zeroed_accum if zeroed_accum is not None else torch.empty((n, _lib.GRAD_STRIDE), **f)
-    entry = lib.cugs_rasterize_backward_prezeroed if zeroed_accum is not None else lib.cugs_rasterize_backward
     if unpack:
         d_rgb, d_opa = torch.empty((n, 3), **f), torch.empty((n,), **f)
         d_means, d_cov = torch.empty((n, 2), **f), torch.empty((n, 3), **f)
@@ -554,52 +529,20 @@ def rasterize_backward(dL_dcolor: torch.Tensor, means_2d: torch.Tensor, cov_2d_i
     if n > 0 and tile_order is not None:
         _torch_check(tile_order.is_contiguous() and tile_order.dtype == torch.int32 and
                      tile_order.numel() == 4 * tile_ranges.shape[0], "tile_order must be a contiguous [tiles, 4] int32 tensor")
-    if n > 0 and want_abs_grad:
+    if n > 0:
         bg = (C.c_float * 3)(*[float(b) for b in background])
-        f32 = lambda t: None if t is None else _f32c(t)
-        check(lib.cugs_rasterize_backward_abs(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                              _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                              _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                              _ptr(opacities.contiguous()), _ptr(packed),
-                                              _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
-                                              _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
-                                              _ptr(d_means), _ptr(d_cov), 1 if zeroed_accum is not None else 0,
-                                              _ptr(tile_order), _ptr(f32(depths)), _ptr(f32(dL_ddepth_map)),
-                                              _ptr(f32(dL_dalpha)), _ptr(d_z), _ptr(d_abs) if unpack else None,
-                                              _stream(dev)),
-              "cugs_rasterize_backward_abs")
-    elif n > 0 and depth_route:
-        bg = (C.c_float * 3)(*[float(b) for b in background])
-        f32 = lambda t: None if t is None else _f32c(t)
-        check(lib.cugs_rasterize_backward_depth(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                                _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                                _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                                _ptr(opacities.contiguous()), _ptr(packed),
-                                                _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
-                                                _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
-                                                _ptr(d_means), _ptr(d_cov), 1 if zeroed_accum is not None else 0,
-                                                _ptr(tile_order), _ptr(_f32c(depths)), _ptr(f32(dL_ddepth_map)),
-                                                _ptr(f32(dL_dalpha)), _ptr(d_z), _stream(dev)),
-              "cugs_rasterize_backward_depth")
-    elif n > 0 and tile_order is not None:
-        bg = (C.c_float * 3)(*[float(b) for b in background])
-        check(lib.cugs_rasterize_backward_ordered(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                                  _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                                  _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                                  _ptr(opacities.contiguous()), _ptr(packed),
-                                                  _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
-                                                  _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
-                                                  _ptr(d_means), _ptr(d_cov), 1 if zeroed_accum is not None else 0,
-                                                  _ptr(tile_order), _stream(dev)), "cugs_rasterize_backward_ordered")
-    elif n > 0:
-        bg = (C.c_float * 3)(*[float(b) for b in background])
-        check(entry(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
-                                          _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
-                                          _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
-                                          _ptr(opacities.contiguous()), _ptr(packed),
-                                          _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
-                                          _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
-                                          _ptr(d_means), _ptr(d_cov), _stream(dev)), "cugs_rasterize_backward")
+        z, g_depth, g_alpha = (None if t is None else _f32c(t) for t in (depths, dL_ddepth_map, dL_dalpha))
+        opts = _lib.BlendBackwardOpts(1 if zeroed_accum is not None else 0, 1 if want_abs_grad else 0, _ptr(tile_order),
+                                      _ptr(z), _ptr(g_depth), _ptr(g_alpha), _ptr(d_z),
+                                      _ptr(d_abs) if unpack else None)    # not unpacked: d_abs is the rows' own words
+        check(lib.cugs_rasterize_backward_opts(int(img_w), int(img_h), bg, _ptr(tile_ranges.contiguous()),
+                                               _ptr(gaussian_indices.contiguous()), _ptr(means_2d.contiguous()),
+                                               _ptr(cov_2d_inv.contiguous()), _ptr(rgb.contiguous()),
+                                               _ptr(opacities.contiguous()), _ptr(packed),
+                                               _ptr(dL_dcolor.contiguous()), _ptr(final_T.contiguous()),
+                                               _ptr(n_contrib.contiguous()), n, _ptr(accum), _ptr(d_rgb), _ptr(d_opa),
+                                               _ptr(d_means), _ptr(d_cov), C.byref(opts), _stream(dev)),
+              "cugs_rasterize_backward_opts")
     return RasterizeBackwardOutput(d_rgb, d_opa, d_means, d_cov, accum, dL_ddepths=d_z, dL_dmeans_2d_abs=d_abs)
 
 

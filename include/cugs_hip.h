@@ -180,7 +180,7 @@ int cugs_sort_pairs_predicted_keyed(int64_t n, int64_t capacity, const float* me
 
 /* cugs_sort_pairs_predicted_keyed that also leaves in tile_order[tiles][4] (16-byte aligned) the tiles ordered by the
  * length of their lists, longest first (to 6 %; empty tiles last), as records {tile, first pair, one past the last pair,
- * 0} - what cugs_rasterize_forward_ordered / cugs_rasterize_backward_ordered hand their workgroups out by (tile and
+ * 0} - what the blends hand their workgroups out by when given as `tile_order` in their options (tile and
  * range in one load).  Not in the reference; what a render() built on this library calls: on views whose splats
  * cluster (every real capture) the blend kernels run a quarter shorter, on uniform ones the same.
  * Whenever the call leaves valid tile ranges it leaves a valid order (every tile once, with its range), misses included. */
@@ -221,51 +221,49 @@ int cugs_rasterize_forward(int width, int height, const float background_host[3]
                            float* out_color, float* out_final_T, int32_t* out_n_contrib,
                            void* stream);
 
-/* The same blend, and in passing a zero-fill of `zero_buf` (zero_bytes: multiple of 16, buffer 16-byte aligned): the
- * blend kernel is bound by instruction issue and leaves HBM idle, so the [n, CUGS_GRAD_STRIDE] accumulator the
- * backward needs is cleared here for free instead of by a fill in front of cugs_rasterize_backward
- * (then call cugs_rasterize_backward_prezeroed). */
-int cugs_rasterize_forward_zero(int width, int height, const float background_host[3],
+/* What the forward blend can do beyond the reference (none of it is in the reference).  Every field may be NULL / 0. */
+typedef struct cugs_blend_forward_opts {
+    /* In passing, a zero-fill of `zero_buf` (zero_bytes: multiple of 16, buffer 16-byte aligned): the blend kernel is
+     * bound by instruction issue and leaves HBM idle, so the [n, CUGS_GRAD_STRIDE] accumulator the backward needs is
+     * cleared here for free instead of by a fill in front of the backward blend (then set
+     * cugs_blend_backward_opts::prezeroed).  An empty image still clears it. */
+    void* zero_buf;
+    size_t zero_bytes;
+    /* The workgroups take their tile AND its range from the records tile_order[0 .. tiles)[4], 16-byte aligned
+     * (cugs_tile_order / cugs_sort_pairs_predicted_keyed_ordered; NULL: the spatial order and tile_ranges).  Any order
+     * of the tiles is a correct one: the outputs do not depend on it, bit for bit; the records must agree with
+     * tile_ranges. */
+    const uint32_t* tile_order;
+    /* The accumulated DEPTH MAP out_depth [H,W], written when either of the two is given:
+     * out_depth[px] = sum_i z_i alpha_i T_i over the same contributors, in the same front-to-back order and with the
+     * same decisions as the colour channels, z_i = depths[i] of cugs_project_forward (the camera-space t.z), bit for
+     * bit; each step is fmaf(alpha_i T_i, z_i, acc) and the background does not enter.  The result equals, bit for bit,
+     * the red channel of this blend with rgb := (z, z, z) and background 0.  color, final_T and n_contrib are those of
+     * the blend without it, bit for bit.  The alpha (coverage) map is 1 - final_T; it needs no output.
+     * depths [n] is then required whenever gaussian_indices is given; out_depth whenever the image is not empty. */
+    const float* depths;
+    float* out_depth;
+} cugs_blend_forward_opts;
+
+/* cugs_rasterize_forward with options (NULL: all off, i.e. cugs_rasterize_forward itself). */
+int cugs_rasterize_forward_opts(int width, int height, const float background_host[3],
                                 const int32_t* tile_ranges, const int32_t* gaussian_indices,
                                 const float* means_2d, const float* cov_2d_inv, const float* rgb,
                                 const float* opacities_act, const float* packed,
                                 float* out_color, float* out_final_T, int32_t* out_n_contrib,
-                                void* zero_buf, size_t zero_bytes, void* stream);
-
-/* cugs_rasterize_forward_zero whose workgroups take their tile AND its range from the records tile_order[0 .. tiles)[4]
- * (cugs_tile_order / cugs_sort_pairs_predicted_keyed_ordered; NULL: the spatial order and tile_ranges).  Any order of the
- * tiles is a correct one: the outputs do not depend on it, bit for bit; the records must agree with tile_ranges.  zero_buf / zero_bytes may be NULL / 0. */
-int cugs_rasterize_forward_ordered(int width, int height, const float background_host[3],
-                                   const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                   const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                   const float* opacities_act, const float* packed, float* out_color,
-                                   float* out_final_T, int32_t* out_n_contrib, void* zero_buf, size_t zero_bytes,
-                                   const uint32_t* tile_order, void* stream);
-
-/* cugs_rasterize_forward_ordered that also writes the accumulated DEPTH MAP out_depth [H,W] (not in the reference;
- * DESIGN.md 4.13): out_depth[px] = sum_i z_i alpha_i T_i over the same contributors, in the same front-to-back order and
- * with the same decisions as the colour channels, z_i = depths[i] of cugs_project_forward (the camera-space t.z), bit for
- * bit; each step is fmaf(alpha_i T_i, z_i, acc) and the background does not enter.  The result equals, bit for bit, the
- * red channel of this blend with rgb := (z, z, z) and background 0.  color, final_T and n_contrib are those of
- * cugs_rasterize_forward_ordered, bit for bit.  The alpha (coverage) map is 1 - final_T; it needs no output.
- * depths [n] is required whenever gaussian_indices is given; out_depth whenever the image is not empty. */
-int cugs_rasterize_forward_depth(int width, int height, const float background_host[3],
-                                 const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                 const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                 const float* opacities_act, const float* packed, float* out_color,
-                                 float* out_final_T, int32_t* out_n_contrib, void* zero_buf, size_t zero_bytes,
-                                 const uint32_t* tile_order, const float* depths, float* out_depth, void* stream);
+                                const cugs_blend_forward_opts* opts, void* stream);
 
 /* ---- a7: rasterize_backward (backward.cu:239-306, kernel :31-233) -------------------
  * grad_accum: [n,CUGS_GRAD_STRIDE] floats, 64-byte aligned scratch (zeroed by the callee).  A row is
  *   {dL_drgb[3], dL_dopacity_act, M1x, M1y, M2xx, M2xy, M2yy, dL_dz, abs_x, abs_y, 0...}
  * Word 9, dL_dz, is the gradient of the depth map with respect to the Gaussian's camera-space depth z (= depths[i]):
- * written by cugs_rasterize_backward_depth only, 0 otherwise.  cugs_project_backward and its fused variants add it to
- * dL/dt.z (t = W p + t_cam), i.e. dL_dpositions += dL_dz * W[2,:], for radii > 0 - a zero word changes no bit.
+ * written on the depth route of cugs_blend_backward_opts only, 0 otherwise.  cugs_project_backward and its fused
+ * variants add it to dL/dt.z (t = W p + t_cam), i.e. dL_dpositions += dL_dz * W[2,:], for radii > 0 - a zero word
+ * changes no bit.
  * Words 10 and 11, abs_x and abs_y, are the ABSOLUTE 2-D mean gradients (AbsGrad): the per-pixel summands of
  * dL_dmeans_2d with fabs around each, abs_x = sum_p |dL/dpower (a dx + b dy)|, abs_y = sum_p |dL/dpower (b dx + c dy)|:
- * written by cugs_rasterize_backward_abs only, 0 otherwise.  They are final, and no other entry point reads them but
- * cugs_densify_accumulate_strided when it is pointed at them.
+ * written with cugs_blend_backward_opts::abs_grad only, 0 otherwise.  They are final, and no other entry point reads
+ * them but cugs_densify_accumulate_strided when it is pointed at them.
  * Words 4..8 are NOT gradients: they are the MOMENTS of dL/dpower over the pixel offsets d = pixel centre - mean,
  *   M1 = sum dL/dpower * (dx, dy),   M2 = sum dL/dpower * (dx^2, dx dy, dy^2),
  * from which the reference's two tensors follow by a per-Gaussian linear map with Sigma'^-1 = (a, b, c)
@@ -283,65 +281,44 @@ int cugs_rasterize_backward(int width, int height, const float background_host[3
                             float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
                             float* dL_dcov_2d_inv, void* stream);
 
-/* cugs_rasterize_backward for a grad_accum that is ALREADY all zeros (cleared by cugs_rasterize_forward_zero since
- * its last use): skips the fill.  Everything else as above. */
-int cugs_rasterize_backward_prezeroed(int width, int height, const float background_host[3],
-                                      const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                      const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                      const float* opacities_act, const float* packed,
-                                      const float* dL_dcolor, const float* final_T,
-                                      const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                      float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                      float* dL_dcov_2d_inv, void* stream);
+/* What the backward blend can do beyond the reference (none of it is in the reference).  Every field may be NULL / 0;
+ * every output that no option touches is the same, up to the order of the atomic adds. */
+typedef struct cugs_blend_backward_opts {
+    /* != 0: grad_accum is ALREADY all zeros (cleared by cugs_blend_forward_opts::zero_buf since its last use): skips
+     * the fill. */
+    int prezeroed;
+    /* != 0: also accumulates the ABSOLUTE 2-D mean gradients (AbsGS / `absgrad`) into words 10 and 11
+     * of each row (layout above): for every contribution the backward blend evaluates, after the gates Q1-Q3 and the
+     * clamp gate, the summand of dL_dmeans_2d with fabs around each component.  Both are >= 0, and 0 for a Gaussian
+     * without a contribution.  On the depth route dL/dpower includes the depth and alpha map terms. */
+    int abs_grad;
+    /* The workgroups are handed out in the order of the records tile_order[0 .. tiles)[4], 16-byte aligned (NULL: the
+     * spatial order).  The sums are the same up to the order of the atomic adds. */
+    const uint32_t* tile_order;
+    /* The DEPTH ROUTE, taken when any of these three is given: the gradients of the DEPTH MAP and the ALPHA MAP
+     * (cugs_blend_forward_opts::out_depth).  dL_ddepth_map [H,W] and dL_dalpha [H,W] (alpha = 1 -
+     * final_T) may each be NULL (zero).  Through the blend they add to dL_dopacity_act and to the moments (words 3..8);
+     * through z they give dL_dz in word 9 of the row.  Colour gradients (words 0..2) are those of dL_dcolor alone.
+     * depths [n] (those of the forward) is then required whenever gaussian_indices is given. */
+    const float* depths;
+    const float* dL_ddepth_map;
+    const float* dL_dalpha;
+    /* dL_ddepths [n] receives word 9: required exactly when the four reference-layout outputs are given on the depth
+     * route, and never off it.  dL_dmeans_2d_abs [n,2] receives words 10 and 11: required exactly when the four are
+     * given with abs_grad.  (CUGS_EINVAL otherwise, before anything is queued.) */
+    float* dL_ddepths;
+    float* dL_dmeans_2d_abs;
+} cugs_blend_backward_opts;
 
-/* cugs_rasterize_backward (prezeroed == 0) or cugs_rasterize_backward_prezeroed (!= 0) with the workgroups handed out in
- * the order of the records tile_order[0 .. tiles)[4] (NULL: the spatial order).  The sums are the same up to the order of
- * the atomic adds. */
-int cugs_rasterize_backward_ordered(int width, int height, const float background_host[3],
-                                    const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                    const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                    const float* opacities_act, const float* packed,
-                                    const float* dL_dcolor, const float* final_T,
-                                    const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                    float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                    float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order, void* stream);
-
-/* cugs_rasterize_backward_ordered with the gradients of the DEPTH MAP and the ALPHA MAP (cugs_rasterize_forward_depth;
- * not in the reference).  dL_ddepth_map [H,W] and dL_dalpha [H,W] (alpha = 1 - final_T) may each be
- * NULL (zero).  Through the blend they add to dL_dopacity_act and to the moments (words 3..8); through z they give
- * dL_dz in word 9 of the row.  Colour gradients (words 0..2) are those of dL_dcolor alone.  depths [n] (those of the
- * forward) is required whenever gaussian_indices is given.  dL_ddepths [n] receives word 9 and is required exactly
- * when the four reference-layout outputs are given (CUGS_EINVAL otherwise). */
-int cugs_rasterize_backward_depth(int width, int height, const float background_host[3],
-                                  const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                  const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                  const float* opacities_act, const float* packed,
-                                  const float* dL_dcolor, const float* final_T,
-                                  const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                  float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                  float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
-                                  const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
-                                  float* dL_ddepths, void* stream);
-
-/* cugs_rasterize_backward_depth that also accumulates the ABSOLUTE 2-D mean gradients (AbsGS / `absgrad`; not in the
- * reference) into words 10 and 11 of each row (layout above): for every contribution the backward blend
- * evaluates, after the gates Q1-Q3 and the clamp gate, the summand of dL_dmeans_2d with fabs around each component.
- * Both are >= 0, and 0 for a Gaussian without a contribution.  depths, dL_ddepth_map and dL_dalpha may ALL be NULL: the
- * colour-only blend (cugs_rasterize_backward_ordered's sums); otherwise they follow cugs_rasterize_backward_depth, and
- * dL/dpower includes the depth and alpha map terms.  dL_dmeans_2d_abs [n,2] receives words 10 and 11 and is required
- * exactly when the four reference-layout outputs are given; dL_ddepths exactly when they are given on the depth route
- * (CUGS_EINVAL otherwise, before anything is queued).  Every other output is that of the entry this one extends, up to
- * the order of the atomic adds. */
-int cugs_rasterize_backward_abs(int width, int height, const float background_host[3],
-                                const int32_t* tile_ranges, const int32_t* gaussian_indices,
-                                const float* means_2d, const float* cov_2d_inv, const float* rgb,
-                                const float* opacities_act, const float* packed,
-                                const float* dL_dcolor, const float* final_T,
-                                const int32_t* n_contrib, int64_t n, float* grad_accum,
-                                float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
-                                float* dL_dcov_2d_inv, int prezeroed, const uint32_t* tile_order,
-                                const float* depths, const float* dL_ddepth_map, const float* dL_dalpha,
-                                float* dL_ddepths, float* dL_dmeans_2d_abs, void* stream);
+/* cugs_rasterize_backward with options (NULL: all off, i.e. cugs_rasterize_backward itself). */
+int cugs_rasterize_backward_opts(int width, int height, const float background_host[3],
+                                 const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                                 const float* means_2d, const float* cov_2d_inv, const float* rgb,
+                                 const float* opacities_act, const float* packed,
+                                 const float* dL_dcolor, const float* final_T,
+                                 const int32_t* n_contrib, int64_t n, float* grad_accum,
+                                 float* dL_drgb, float* dL_dopacity_act, float* dL_dmeans_2d,
+                                 float* dL_dcov_2d_inv, const cugs_blend_backward_opts* opts, void* stream);
 
 /* ---- a8+a9: project_backward (projection_backward.cu:253-344, kernel :26-247) -------
  * One launch: k_project_backward + directions + k_evaluate_sh_backward.  The incoming 2-D
@@ -462,8 +439,8 @@ int cugs_eval_metrics(int width, int height, const float* rendered, const float*
  *   Gaussian max_radii_2d = max(max_radii_2d, radii).  All three accumulators are float [n].
  * cugs_densify_accumulate_strided: the same, bit for bit, reading Gaussian i's gradient at
  *   dL_dmeans_2d[i * row_stride_floats + {0, 1}] (row_stride_floats >= 2, CUGS_EINVAL otherwise; even and the base
- *   8-byte aligned, CUGS_EALIGN otherwise): pointed at word 10 of cugs_rasterize_backward_abs's rows with stride
- *   CUGS_GRAD_STRIDE it accumulates the AbsGrad norm with no intermediate tensor.
+ *   8-byte aligned, CUGS_EALIGN otherwise): pointed at word 10 of the rows cugs_blend_backward_opts::abs_grad leaves,
+ *   with stride CUGS_GRAD_STRIDE, it accumulates the AbsGrad norm with no intermediate tensor.
  * cugs_densify_classify: compute_clone_mask / compute_split_mask / compute_keep_mask (:351-442) as one
  *   byte per Gaussian: bit 0 clone candidate, bit 1 split candidate, bit 2 keep.  The thresholds are the
  *   reference's float products (size = percent_dense * scene_extent, ws = 0.1f * scene_extent);

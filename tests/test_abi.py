@@ -69,6 +69,13 @@ def test_argument_validation_without_gpu(pkg):
     bg = (C.c_float * 3)(0, 0, 0)
     assert lib.cugs_rasterize_backward(16, 16, bg, null, null, null, null, null, null, null, null, null, null, 4,
                                        C.c_void_p(0x1004), null, null, null, null, null) == -2
+    # the same through the entry with options: none (NULL), then a misaligned tile_order in them
+    assert lib.cugs_rasterize_backward_opts(16, 16, bg, null, null, null, null, null, null, null, null, null, null, 4,
+                                            C.c_void_p(0x1004), null, null, null, null, None, null) == -2
+    from cugs_amd._lib import BlendBackwardOpts
+    opts = BlendBackwardOpts(prezeroed=1, tile_order=0x2004)
+    assert lib.cugs_rasterize_backward_opts(16, 16, bg, null, null, null, null, null, null, null, null, null, null, 4,
+                                            C.c_void_p(0x1000), null, null, null, null, C.byref(opts), null) == -2   # CUGS_EALIGN
     # the gated colour gradient on its own (data-parallel early gather)
     assert lib.cugs_gated_colour_grad(-1, null, null, null, null) == -1
     assert lib.cugs_gated_colour_grad(0, null, null, null, null) == 0

@@ -1,5 +1,5 @@
-"""cugs_rasterize_backward_abs / cugs_densify_accumulate_strided: argument validation that fails before anything
-touches the device (no GPU needed)."""
+"""cugs_rasterize_backward_opts with abs_grad / cugs_densify_accumulate_strided: argument validation that fails before
+anything touches the device (no GPU needed)."""
 import ctypes as C
 
 EINVAL, EALIGN = -1, -2
@@ -13,14 +13,17 @@ def _bwd(lib, soa, d_abs, d_depths=NUL, depths=NUL, dD=NUL, dA=NUL, n=10):
     b = FAKE if soa >= 2 else NUL
     c = FAKE if soa >= 3 else NUL
     d = FAKE if soa >= 4 else NUL
+    from cugs_amd._lib import BlendBackwardOpts
     # prezeroed = 1: no fill is queued before the checks
-    return lib.cugs_rasterize_backward_abs(32, 32, BG, FAKE, FAKE, NUL, NUL, NUL, NUL, FAKE, FAKE, FAKE, FAKE, n, FAKE,
-                                           a, b, c, d, 1, NUL, depths, dD, dA, d_depths, d_abs, NUL)
+    opts = BlendBackwardOpts(prezeroed=1, abs_grad=1, depths=depths, dL_ddepth_map=dD, dL_dalpha=dA, dL_ddepths=d_depths,
+                             dL_dmeans_2d_abs=d_abs)
+    return lib.cugs_rasterize_backward_opts(32, 32, BG, FAKE, FAKE, NUL, NUL, NUL, NUL, FAKE, FAKE, FAKE, FAKE, n, FAKE,
+                                            a, b, c, d, C.byref(opts), NUL)
 
 
 def test_absgrad_symbols_bound(pkg):
     from cugs_amd import _lib
-    for name in ("cugs_rasterize_backward_abs", "cugs_densify_accumulate_strided"):
+    for name in ("cugs_rasterize_backward_opts", "cugs_densify_accumulate_strided"):
         assert name in _lib.SIGNATURES
         assert getattr(C.CDLL(pkg.LIB_PATH), name)
 

@@ -1,6 +1,6 @@
-"""cugs_rasterize_forward_depth / cugs_rasterize_backward_depth: argument validation that fails before anything touches
-the device (no GPU needed): CUGS_EINVAL (-1) for a missing depth input or output and for partial reference-layout
-outputs, 0 for the empty no-op."""
+"""The depth options of cugs_rasterize_forward_opts / cugs_rasterize_backward_opts: argument validation that fails
+before anything touches the device (no GPU needed): CUGS_EINVAL (-1) for a missing depth input or output and for
+partial reference-layout outputs, 0 for the empty no-op."""
 import ctypes as C
 
 EINVAL = -1
@@ -10,8 +10,10 @@ BG = (C.c_float * 3)(0.0, 0.0, 0.0)
 
 
 def _fwd(lib, depths, out_depth, w=32, h=32, indices=FAKE):
-    return lib.cugs_rasterize_forward_depth(w, h, BG, FAKE, indices, NUL, NUL, NUL, NUL, FAKE, FAKE, FAKE, FAKE, NUL,
-                                            0, NUL, depths, out_depth, NUL)
+    from cugs_amd._lib import BlendForwardOpts
+    opts = BlendForwardOpts(depths=depths, out_depth=out_depth)
+    return lib.cugs_rasterize_forward_opts(w, h, BG, FAKE, indices, NUL, NUL, NUL, NUL, FAKE, FAKE, FAKE, FAKE,
+                                           C.byref(opts), NUL)
 
 
 def _bwd(lib, soa, d_depths, depths=FAKE, n=10):
@@ -19,14 +21,16 @@ def _bwd(lib, soa, d_depths, depths=FAKE, n=10):
     b = FAKE if soa >= 2 else NUL
     c = FAKE if soa >= 3 else NUL
     d = FAKE if soa >= 4 else NUL
+    from cugs_amd._lib import BlendBackwardOpts
     # prezeroed = 1: no fill is queued before the checks
-    return lib.cugs_rasterize_backward_depth(32, 32, BG, FAKE, FAKE, NUL, NUL, NUL, NUL, FAKE, FAKE, FAKE, FAKE, n, FAKE,
-                                             a, b, c, d, 1, NUL, depths, FAKE, FAKE, d_depths, NUL)
+    opts = BlendBackwardOpts(prezeroed=1, depths=depths, dL_ddepth_map=FAKE, dL_dalpha=FAKE, dL_ddepths=d_depths)
+    return lib.cugs_rasterize_backward_opts(32, 32, BG, FAKE, FAKE, NUL, NUL, NUL, NUL, FAKE, FAKE, FAKE, FAKE, n, FAKE,
+                                            a, b, c, d, C.byref(opts), NUL)
 
 
 def test_depth_map_symbols_bound(pkg):
     from cugs_amd import _lib
-    for name in ("cugs_rasterize_forward_depth", "cugs_rasterize_backward_depth"):
+    for name in ("cugs_rasterize_forward_opts", "cugs_rasterize_backward_opts"):
         assert name in _lib.SIGNATURES
         assert getattr(C.CDLL(pkg.LIB_PATH), name)
 

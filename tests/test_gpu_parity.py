@@ -885,7 +885,7 @@ def test_backward_with_clamped_alphas_and_tiny_images(pkg, orc, dev):
 
 
 def test_forward_blend_clears_the_backward_accumulator(pkg, orc, dev):
-    """cugs_rasterize_forward_zero / cugs_rasterize_backward_prezeroed: the forward blend fills a DIRTY buffer with
+    """cugs_blend_forward_opts::zero_buf / cugs_blend_backward_opts::prezeroed: the forward blend fills a DIRTY buffer with
     zeros while it renders (image bit-equal to the plain entry), the backward run on that buffer without its own
     fill gives the gradients of the filling path (<= 1e-5: atomics reorder sums), an odd-sized buffer is covered to
     its last 16 bytes, a misaligned one is refused, and a RenderOutput hands its cleared accumulator out ONCE - a
