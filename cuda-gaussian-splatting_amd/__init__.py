@@ -17,7 +17,9 @@ from .rasterizer import (evaluate_sh_backward_cuda, evaluate_sh_cuda, project_ba
                          sh_backward_views, sort_gaussians)
 from .fused_adam import (AdamConfig, FusedAdam, ParamGroup, PositionLRConfig,  # noqa: F401
                          active_sh_degree_for_step, lr_defaults, position_lr)
-from .loss import combined_loss, combined_loss_and_grad, l1_loss, ssim, ssim_loss  # noqa: F401
+from .loss import (ExposureLoss, combined_loss, combined_loss_and_grad, combined_loss_exposure, l1_loss, ssim,  # noqa: F401
+                   ssim_loss)
+from .exposure import ExposureModel  # noqa: F401
 from .densification import DensificationConfig, DensificationController, DensificationStats  # noqa: F401
 from .mcmc import MCMCConfig, MCMCController, MCMCStats  # noqa: F401
 from .gaussian_init import init_gaussians_from_sparse, knn_mean_distances  # noqa: F401

@@ -74,6 +74,11 @@ class BlendBackwardOpts(C.Structure):
                 ("dL_ddepth_map", C.c_void_p), ("dL_dalpha", C.c_void_p), ("dL_ddepths", C.c_void_p),
                 ("dL_dmeans_2d_abs", C.c_void_p)]
 
+
+class LossOpts(C.Structure):
+    """struct cugs_loss_opts."""
+    _fields_ = [("exposure", C.c_void_p), ("mask", C.c_void_p), ("dL_dexposure", C.c_void_p), ("corrected", C.c_void_p)]
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -128,6 +133,8 @@ SIGNATURES = {
     "cugs_fused_adam_groups": (_I, [C.POINTER(AdamGroup), _I, _F, _F, _F, _F, _F, _P]),
     "cugs_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_combined_loss": (_I, [_I, _I, _P, _P, _F, _I, _P, C.c_size_t, _P, _P, _P, _P]),
+    "cugs_loss_opts_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "cugs_combined_loss_opts": (_I, [_I, _I, _P, _P, _F, _I, C.POINTER(LossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_eval_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_eval_metrics": (_I, [_I, _I, _P, _P, _P, _I, _P, C.c_size_t, _P, _P]),
     "cugs_densify_accumulate": (_I, [_L, _P, _P, _P, _P, _P, _P]),

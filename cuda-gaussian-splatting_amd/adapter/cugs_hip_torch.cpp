@@ -646,6 +646,45 @@ torch::Tensor ssim(const torch::Tensor& rendered, const torch::Tensor& target, i
     return map;
 }
 
+ExposureLoss combined_loss_exposure(const torch::Tensor& rendered, const torch::Tensor& target, float lambda_,
+                                    const torch::Tensor& exposure, const torch::Tensor& mask, bool want_grad,
+                                    bool want_corrected, int window_size) {
+    validate_pair(rendered, target);
+    TORCH_CHECK(window_size % 2 == 1, "window_size must be odd, got ", window_size);
+    TORCH_CHECK(window_size >= 3, "window_size must be >= 3, got ", window_size);
+    const int h = static_cast<int>(rendered.size(0)), w = static_cast<int>(rendered.size(1));
+    if (exposure.defined()) {
+        TORCH_CHECK(exposure.dim() == 2 && exposure.size(0) == 3 && exposure.size(1) == 4, "exposure must be [3, 4], got ", exposure.sizes());
+        TORCH_CHECK(exposure.dtype() == torch::kFloat32, "exposure must be float32, got ", exposure.dtype());
+        TORCH_CHECK(exposure.is_cuda() && exposure.device() == rendered.device(), "exposure must be on the images' CUDA device");
+        TORCH_CHECK(exposure.is_contiguous(), "exposure must be contiguous");
+    }
+    torch::Tensor m;
+    if (mask.defined()) {
+        TORCH_CHECK(mask.dim() == 2 && mask.size(0) == h && mask.size(1) == w, "mask must be [H, W], got ", mask.sizes());
+        TORCH_CHECK(mask.dtype() == torch::kFloat32, "mask must be float32, got ", mask.dtype());
+        TORCH_CHECK(mask.is_cuda() && mask.device() == rendered.device(), "mask must be on the images' CUDA device");
+        m = mask.contiguous();
+    }
+    auto r = rendered.contiguous(), t = target.contiguous();
+    auto out = torch::empty({4}, fopt(rendered));
+    ExposureLoss o;
+    if (want_grad) o.dL_dcolor = torch::empty({h, w, 3}, fopt(rendered));
+    if (want_grad && exposure.defined()) o.dL_dexposure = torch::empty({3, 4}, fopt(rendered));
+    if (want_corrected) o.corrected = torch::empty({h, w, 3}, fopt(rendered));
+    cugs_loss_opts opts{};
+    opts.exposure = exposure.defined() ? exposure.data_ptr<float>() : nullptr;
+    opts.mask = m.defined() ? m.data_ptr<float>() : nullptr;
+    opts.dL_dexposure = o.dL_dexposure.defined() ? o.dL_dexposure.data_ptr<float>() : nullptr;
+    opts.corrected = o.corrected.defined() ? o.corrected.data_ptr<float>() : nullptr;
+    auto ws = workspace(rendered.device(), cugs_loss_opts_workspace_bytes(w, h), 2);
+    check(cugs_combined_loss_opts(w, h, ptr<float>(r), ptr<float>(t), lambda_, window_size, &opts, ws.data_ptr(), ws.numel(),
+                                  ptr<float>(out), nullptr, want_grad ? o.dL_dcolor.data_ptr<float>() : nullptr,
+                                  stream_of(rendered)), "cugs_combined_loss_opts");
+    o.loss = out[0]; o.l1 = out[1]; o.ssim_mean = out[2];
+    return o;
+}
+
 FusedAdam::FusedAdam(std::array<torch::Tensor, 5> params, std::array<float, 5> lrs, AdamHyper h)
     : params_(std::move(params)), lrs_(lrs), h_(h) {
     for (int i = 0; i < 5; ++i) { m_[i] = torch::zeros_like(params_[i]); v_[i] = torch::zeros_like(params_[i]); }

@@ -145,6 +145,17 @@ LossAndGrad combined_loss_and_grad(const torch::Tensor& rendered, const torch::T
 torch::Tensor combined_loss(const torch::Tensor& rendered, const torch::Tensor& target, float lambda_ = 0.2f);
 torch::Tensor ssim(const torch::Tensor& rendered, const torch::Tensor& target, int window_size = 11);
 
+// Not in the reference: the same loss of x' = mask * (A rendered + b) against y' = mask * target, inside
+// the same two launches.  `exposure`: float32 [3,4] = [A | b], contiguous, on the images' device (undefined: identity);
+// `mask`: float32 [H,W] (undefined: all ones).  Both means stay over all 3 H W elements.  dL_dcolor = mask A^T dL/dx'
+// (with want_grad), dL_dexposure [3,4] (with want_grad and an exposure; twelve fixed-order fp64 sums, the same bits
+// from run to run), corrected = x' (with want_corrected); no gradient to the mask or the target, no host sync.
+// With neither exposure nor mask nor want_corrected: combined_loss_and_grad, bit for bit.
+struct ExposureLoss { torch::Tensor loss, dL_dcolor, dL_dexposure, l1, ssim_mean, corrected; };
+ExposureLoss combined_loss_exposure(const torch::Tensor& rendered, const torch::Tensor& target, float lambda_ = 0.2f,
+                                    const torch::Tensor& exposure = {}, const torch::Tensor& mask = {},
+                                    bool want_grad = true, bool want_corrected = false, int window_size = 11);
+
 // optimizer/fused_adam.hpp:29-106 on raw tensors (group order: positions, sh, opacities, scales, rotations)
 struct AdamHyper { float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-15f; };
 class FusedAdam {

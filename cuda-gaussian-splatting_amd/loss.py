@@ -1,15 +1,17 @@
 """Host-side mirror of the reference's loss surface (src/training/loss.hpp:21-52) over the fused HIP
 kernels (csrc/loss.hip): l1_loss, ssim, ssim_loss, combined_loss - plus combined_loss_and_grad, which
 returns the loss together with dL/dcolor, i.e. what trainer.cpp:214-217 obtains with clone + autograd + clone.
+combined_loss_exposure (not in the reference) is the same loss behind a per-view 3x4 exposure matrix
+and an optional pixel mask, both applied inside the same two kernels.
 Scalars come back as 0-dim device tensors (no host sync), as in the reference."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from ._lib import check, lib
+from ._lib import LossOpts, check, lib
 from .rasterizer import _ptr, _stream, _torch_check, _workspace
 
 
@@ -67,3 +69,51 @@ def combined_loss_and_grad(rendered: torch.Tensor, target: torch.Tensor,
     """(loss, dL_dcolor [H,W,3]) in two launches: replaces clone + combined_loss + backward + clone."""
     out, _, grad = _run(rendered, target, lambda_, 11, False, True)
     return out[0], grad
+
+
+class ExposureLoss(NamedTuple):
+    """combined_loss_exposure's results; dL_dcolor, dL_dexposure and corrected are None when not asked for."""
+    loss: torch.Tensor                       # 0-dim
+    dL_dcolor: Optional[torch.Tensor]        # [H,W,3] = m A^T dL/dx'
+    dL_dexposure: Optional[torch.Tensor]     # [3,4]
+    l1: torch.Tensor                         # 0-dim
+    ssim_mean: torch.Tensor                  # 0-dim
+    corrected: Optional[torch.Tensor]        # [H,W,3] = x'
+
+
+def combined_loss_exposure(rendered: torch.Tensor, target: torch.Tensor, lambda_: float = 0.2,
+                           exposure: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                           want_grad: bool = True, want_corrected: bool = False,
+                           window_size: int = 11) -> ExposureLoss:
+    """combined_loss of x' = mask * (A @ rendered + b) against y' = mask * target, with exposure = [A | b] a float32
+    [3,4] device tensor (None: the identity) and mask a float32 [H,W] device tensor of weights (None: all ones).  Both
+    means stay over all 3*H*W elements, so a masked pixel counts as a perfect one.  With want_grad the result carries
+    dL_dcolor (ready for render_backward) and, when an exposure is given, dL_dexposure [3,4]: twelve fixed-order fp64
+    sums, the same bits from run to run.  No gradient flows to the mask or the target.  Still two launches over the
+    image (plus a one-workgroup reduction for dL_dexposure) and no host sync.  With neither exposure nor mask (and no
+    want_corrected) this is combined_loss_and_grad, bit for bit."""
+    _validate_pair(rendered, target)
+    _torch_check(window_size % 2 == 1, f"window_size must be odd, got {window_size}")
+    _torch_check(window_size >= 3, f"window_size must be >= 3, got {window_size}")
+    h, w = int(rendered.shape[0]), int(rendered.shape[1])
+    dev = rendered.device
+    if exposure is not None:
+        _torch_check(tuple(exposure.shape) == (3, 4), f"exposure must be [3, 4], got {tuple(exposure.shape)}")
+        _torch_check(exposure.dtype == torch.float32, f"exposure must be float32, got {exposure.dtype}")
+        _torch_check(exposure.is_cuda and exposure.device == dev, "exposure must be on the images' CUDA device")
+        _torch_check(exposure.is_contiguous(), "exposure must be contiguous (a row of ExposureModel.params is)")
+    if mask is not None:
+        _torch_check(tuple(mask.shape) == (h, w), f"mask must be [H, W] = {(h, w)}, got {tuple(mask.shape)}")
+        _torch_check(mask.dtype == torch.float32, f"mask must be float32, got {mask.dtype}")
+        _torch_check(mask.is_cuda and mask.device == dev, "mask must be on the images' CUDA device")
+        mask = mask.contiguous()
+    r, t = rendered.contiguous(), target.contiguous()
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    grad = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if want_grad else None
+    d_exp = torch.empty((3, 4), dtype=torch.float32, device=dev) if want_grad and exposure is not None else None
+    corrected = torch.empty((h, w, 3), dtype=torch.float32, device=dev) if want_corrected else None
+    opts = LossOpts(exposure=_ptr(exposure), mask=_ptr(mask), dL_dexposure=_ptr(d_exp), corrected=_ptr(corrected))
+    ws = _workspace(dev, lib.cugs_loss_opts_workspace_bytes(w, h), "loss")
+    check(lib.cugs_combined_loss_opts(w, h, _ptr(r), _ptr(t), float(lambda_), int(window_size), C.byref(opts), _ptr(ws),
+                                      ws.numel(), _ptr(out), None, _ptr(grad), _stream(dev)), "cugs_combined_loss_opts")
+    return ExposureLoss(out[0], grad, d_exp, out[1], out[2], corrected)

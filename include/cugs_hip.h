@@ -417,6 +417,27 @@ int cugs_combined_loss(int width, int height, const float* rendered, const float
                        int window_size, void* workspace, size_t workspace_bytes, float* loss_out,
                        float* ssim_map, float* dL_dcolor, void* stream);
 
+/* ---- Per-view exposure compensation and pixel masks in the fused loss (not in the reference) ----
+ * The same loss of x'(p) = m(p) (A c(p) + b) against y'(p) = m(p) y(p): c = rendered, y = target, E = [A | b] a
+ * row-major 3x4 matrix, m a per-pixel weight.  Both means stay over all 3 H W elements whatever the mask, and the SSIM
+ * window's zero padding applies to x' and y' (a pixel outside the image is 0, not b).  With g = dL/dx':
+ *   dL_dcolor(p) = m(p) A^T g(p),   dL_dexposure[4 i + j] = sum_p m(p) g_i(p) c_j(p)  (j = 3: sum_p m(p) g_i(p)),
+ * the twelve sums in fp64 in a fixed order (per-tile partials, then one workgroup): the same bits from run to run, no
+ * float atomics, no host sync.  No gradient flows to the mask or the target.  ssim_map is the map of (x', y').
+ * Every field may be NULL; opts == NULL or all NULL runs the kernels of cugs_combined_loss and gives its bits.
+ * CUGS_EINVAL for dL_dexposure without exposure or without dL_dcolor; otherwise the checks of cugs_combined_loss
+ * against cugs_loss_opts_workspace_bytes (CUGS_EWORKSPACE for a short workspace), all before anything is queued. */
+typedef struct cugs_loss_opts {
+    const float* exposure;      /* DEVICE float[12], row-major [A | b]; NULL: identity */
+    const float* mask;          /* DEVICE float[H*W]; NULL: all ones */
+    float*       dL_dexposure;  /* DEVICE float[12]; needs exposure and dL_dcolor */
+    float*       corrected;     /* DEVICE float[H*W*3], x' */
+} cugs_loss_opts;
+size_t cugs_loss_opts_workspace_bytes(int width, int height);
+int cugs_combined_loss_opts(int width, int height, const float* rendered, const float* target, float lambda,
+                            int window_size, const cugs_loss_opts* opts, void* workspace, size_t workspace_bytes,
+                            float* loss_out, float* ssim_map, float* dL_dcolor, void* stream);
+
 /* ---- Evaluation metrics of one view (training/metrics.cpp:21-46: compute_psnr, compute_ssim) ---------------
  * rendered: [H,W,3] float.  The target is EITHER target_f32 ([H,W,3] float) OR target_u8 ([H,W,3] uint8, a cached
  * view at the camera's size, expanded in registers as (float)b * (1.0f / 255.0f): the bits of cugs_image_to_float

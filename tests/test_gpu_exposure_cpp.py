@@ -1,0 +1,42 @@
+"""The exposure-compensated, masked loss through the C++ host (cuda-gaussian-splatting_amd/adapter:
+cugs_hip::combined_loss_exposure) run as a native program (adapter/exposure_driver.bin) on the same raw inputs as the
+Python host: the same bytes in every output."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import exposure_ref as er
+from util import np_
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "exposure_driver.bin")
+
+
+def test_cpp_exposure_loss_matches_python_host(pkg, dev, tmp_path):
+    if not os.path.exists(DRIVER):
+        pytest.skip("exposure_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
+    shapes = [(7, 5), (37, 53), (64, 64)]
+    manifest = [f"cases {len(shapes)}"]
+    for i, (h, w) in enumerate(shapes):
+        c, t, E, mask = er.make_case(h, w)
+        for name, a in (("c", c), ("t", t), ("e", E), ("m", mask)):
+            a.numpy().tofile(tmp_path / f"case_{i}_{name}.f32")
+        manifest.append(f"{h} {w} 1 0.2")
+    (tmp_path / "manifest.txt").write_text("\n".join(manifest) + "\n")
+
+    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    assert f"exposure_driver ok cases={len(shapes)} bad_exposure_throws=1" in res.stdout
+
+    for i, (h, w) in enumerate(shapes):
+        c, t, E, mask = (a.to(dev) for a in er.make_case(h, w))
+        want = pkg.combined_loss_exposure(c, t, 0.2, exposure=E, mask=mask, want_corrected=True)
+        got = {k: np.fromfile(tmp_path / f"out_{i}_{k}.f32", np.float32) for k in ("loss", "dc", "de", "x")}
+        scalars = np.array([float(want.loss), float(want.l1), float(want.ssim_mean)], np.float32)
+        assert got["loss"].tobytes() == scalars.tobytes(), (i, got["loss"], scalars)
+        assert got["dc"].tobytes() == np_(want.dL_dcolor).tobytes(), i
+        assert got["de"].tobytes() == np_(want.dL_dexposure).tobytes(), i
+        assert got["x"].tobytes() == np_(want.corrected).tobytes(), i
