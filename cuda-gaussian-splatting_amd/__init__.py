@@ -28,4 +28,6 @@ from . import pose  # noqa: F401
 from .ply_io import read_gaussian_ply, restore_optimizer, write_gaussian_ply  # noqa: F401
 from .views import StreamedViewCache, ViewCache, image_to_float, load_image_resized, load_image_u8  # noqa: F401
 from .metrics import EvalResults, ImageMetrics, compute_psnr, compute_ssim, eval_metrics, evaluate  # noqa: F401
+from .importance import (ContributionScores, accumulate_contribution_scores, blend_scores,  # noqa: F401
+                         contribution_scores, prune_by_scores, prune_gaussians)
 from . import parallel, scene  # noqa: F401

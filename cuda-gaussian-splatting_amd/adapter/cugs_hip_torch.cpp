@@ -1246,4 +1246,121 @@ ModelTensors init_gaussians_from_sparse(const torch::Tensor& positions, const to
     return m;
 }
 
+// ---- contribution scores and score-based pruning ----
+ContributionScores::ContributionScores(int64_t n, const torch::Device& device)
+    : table(torch::zeros({n, 4}, torch::TensorOptions().dtype(torch::kInt32).device(device))) {}
+torch::Tensor ContributionScores::weight_sum() const { return table.view(torch::kFloat32).select(1, 0); }
+torch::Tensor ContributionScores::weight_max() const { return table.view(torch::kFloat32).select(1, 1); }
+torch::Tensor ContributionScores::pixel_count() const {
+    return table.select(1, 2).to(torch::kInt64).bitwise_and(static_cast<int64_t>(0xFFFFFFFFll));
+}
+void ContributionScores::reset() { table.zero_(); num_views = 0; }
+
+namespace {
+void launch_scores(ContributionScores& scores, int width, int height, const torch::Tensor& tile_ranges,
+                   const torch::Tensor& gaussian_indices, const torch::Tensor& means_2d, const torch::Tensor& cov_2d_inv,
+                   const torch::Tensor& opacities_act, const torch::Tensor& packed, const torch::Tensor& tile_order) {
+    auto tr = tile_ranges.contiguous(), gi = gaussian_indices.contiguous();
+    auto m = means_2d.contiguous(), c = cov_2d_inv.contiguous(), op = opacities_act.contiguous();
+    auto pk = packed.defined() ? packed.contiguous() : packed;
+    if (tile_order.defined())
+        TORCH_CHECK(tile_order.is_contiguous() && tile_order.scalar_type() == torch::kInt32 &&
+                    tile_order.numel() == 4 * tr.size(0), "tile_order must be a contiguous [tiles, 4] int32 tensor");
+    check(cugs_blend_scores(width, height, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m), ptr<float>(c), ptr<float>(op),
+                            ptr<float>(pk), order_ptr(tile_order), static_cast<int>(scores.n()),
+                            scores.n() > 0 ? scores.table.data_ptr() : nullptr, stream_of(scores.table)),
+          "cugs_blend_scores");
+    ++scores.num_views;
+}
+}  // namespace
+
+void accumulate_contribution_scores(ContributionScores& scores, const RenderOutput& out, const cugs_camera& camera) {
+    const int64_t n = out.means_2d.size(0);
+    TORCH_CHECK(n == scores.n(), "accumulate_contribution_scores: the table holds ", scores.n(), " Gaussians, the render ", n);
+    if (n == 0) { ++scores.num_views; return; }
+    TORCH_CHECK(out.means_2d.device() == scores.table.device(), "accumulate_contribution_scores: the score table is on another device");
+    launch_scores(scores, camera.width, camera.height, out.tile_ranges, out.gaussian_indices, out.means_2d, out.cov_2d_inv,
+                  out.opacities_act, out.packed, out.tile_order);
+}
+
+ContributionScores contribution_scores(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                                       const RenderSettings& settings) {
+    TORCH_CHECK(model.positions.is_cuda(), "GaussianModel must be on CUDA device");
+    const int64_t n = model.positions.size(0);
+    ContributionScores scores(n, model.positions.device());
+    for (const auto& cam : cameras) {
+        if (n == 0) { ++scores.num_views; continue; }
+        auto proj = project_gaussians(model.positions, model.rotations, model.scales, model.opacities, model.sh_coeffs, cam,
+                                      0, settings.scale_modifier);             // degree 0: the colour is not used
+        auto srt = sort_gaussians(proj.means_2d, proj.depths, proj.radii, proj.tiles_touched, cam.width, cam.height);
+        launch_scores(scores, cam.width, cam.height, srt.tile_ranges, srt.gaussian_values_sorted, proj.means_2d,
+                      proj.cov_2d_inv, proj.opacities_act, proj.packed, {});
+    }
+    return scores;
+}
+
+int64_t prune_gaussians(ModelTensors& model, const torch::Tensor& prune_mask, FusedAdam* optimizer) {
+    torch::NoGradGuard no_grad;
+    const int64_t n = model.positions.size(0);
+    TORCH_CHECK(model.positions.is_cuda(), "prune_gaussians: model must be on CUDA");
+    TORCH_CHECK(prune_mask.defined() && prune_mask.scalar_type() == torch::kBool && prune_mask.dim() == 1 &&
+                prune_mask.size(0) == n, "prune_gaussians: prune_mask must be a bool tensor of shape [", n, "]");
+    TORCH_CHECK(prune_mask.device() == model.positions.device(), "prune_gaussians: prune_mask must be on the model's device");
+    if (n == 0) return 0;
+    const auto dev = model.positions.device();
+    void* st = stream_of(model.positions);
+    auto flags = prune_mask.logical_not().to(torch::kUInt8).bitwise_left_shift(2).contiguous();   // bit 2: keep
+    auto ws = workspace(dev, cugs_densify_workspace_bytes(n), 3);
+    int64_t counts[4];
+    check(cugs_densify_plan(n, flags.data_ptr<uint8_t>(), ws.data_ptr(), ws.numel(), counts, st), "cugs_densify_plan");
+    const int64_t n_out = counts[3];
+    if (n_out == n) return 0;
+    std::vector<torch::Tensor> srcs, dsts;
+    std::vector<cugs_densify_array> desc;
+    auto add = [&](const torch::Tensor& src, int mode) {
+        auto s = src.contiguous();
+        auto sizes = s.sizes().vec();
+        sizes[0] = n_out;
+        auto d = torch::empty(sizes, fopt(model.positions));
+        srcs.push_back(s); dsts.push_back(d);
+        desc.push_back(cugs_densify_array{s.data_ptr<float>(), d.data_ptr<float>(), static_cast<int32_t>(s.numel() / n), mode});
+        return d;
+    };
+    auto new_pos = add(model.positions, CUGS_DENSIFY_COPY), new_sh = add(model.sh_coeffs, CUGS_DENSIFY_COPY);
+    auto new_opa = add(model.opacities, CUGS_DENSIFY_COPY), new_rot = add(model.rotations, CUGS_DENSIFY_COPY);
+    auto new_scl = add(model.scales, CUGS_DENSIFY_COPY);
+    std::array<torch::Tensor, 5> nm, nv;
+    if (optimizer) for (int i = 0; i < 5; ++i) { nm[i] = add(optimizer->m_[i], CUGS_DENSIFY_STATE); nv[i] = add(optimizer->v_[i], CUGS_DENSIFY_STATE); }
+    if (n_out > 0)
+        check(cugs_densify_apply(n, n_out, ws.data_ptr(), ws.numel(), nullptr, nullptr, desc.data(),
+                                 static_cast<int>(desc.size()), st), "cugs_densify_apply");
+    model.positions = new_pos; model.sh_coeffs = new_sh; model.opacities = new_opa; model.rotations = new_rot; model.scales = new_scl;
+    if (optimizer) {
+        optimizer->params_ = {model.positions, model.sh_coeffs, model.opacities, model.scales, model.rotations};
+        optimizer->m_ = nm; optimizer->v_ = nv;
+        optimizer->zero_grad();
+    }
+    return n - n_out;
+}
+
+int64_t prune_by_scores(ModelTensors& model, const ContributionScores& scores, float min_max_weight, float keep_fraction,
+                        FusedAdam* optimizer) {
+    const int64_t n = model.positions.size(0);
+    TORCH_CHECK(scores.n() == n, "prune_by_scores: the table holds ", scores.n(), " Gaussians, the model ", n);
+    TORCH_CHECK(min_max_weight >= 0.0f || keep_fraction >= 0.0f, "prune_by_scores: give min_max_weight, keep_fraction or both");
+    if (n == 0) return 0;
+    TORCH_CHECK(scores.table.device() == model.positions.device(), "prune_by_scores: the score table is on another device");
+    const auto wmax = scores.weight_max();
+    auto mask = wmax.eq(0.0f);
+    if (min_max_weight >= 0.0f) mask = mask.logical_or(wmax.lt(min_max_weight));
+    if (keep_fraction >= 0.0f) {
+        TORCH_CHECK(keep_fraction <= 1.0f, "prune_by_scores: keep_fraction must lie in [0, 1]");
+        const int64_t keep = std::llround(static_cast<double>(keep_fraction) * static_cast<double>(n));
+        auto drop = torch::ones({n}, torch::TensorOptions().dtype(torch::kBool).device(mask.device()));
+        if (keep > 0) drop.index_fill_(0, std::get<1>(scores.weight_sum().topk(keep)), false);
+        mask = mask.logical_or(drop);
+    }
+    return prune_gaussians(model, mask, optimizer);
+}
+
 }  // namespace cugs_hip

@@ -170,9 +170,12 @@ public:
     // corrections for the launch that updates the parameters in place (they must be contiguous float32).
     cugs_adam_fused begin_fused_step();
     const std::array<torch::Tensor, 5>& params() const { return params_; }
+    const std::array<torch::Tensor, 5>& exp_avg() const { return m_; }          // first / second moments, group order
+    const std::array<torch::Tensor, 5>& exp_avg_sq() const { return v_; }
 private:
     friend class DensificationController;      // carries m_/v_ through clone/split/prune
     friend class MCMCController;               // zeroes the relocated rows' moments
+    friend int64_t prune_gaussians(ModelTensors&, const torch::Tensor&, FusedAdam*);   // carries m_/v_ through the prune
     friend bool write_gaussian_ply(const std::string&, const ModelTensors&, const FusedAdam*);
     friend ModelTensors read_gaussian_ply(const std::string&, const torch::Device&, FusedAdam*);
     std::array<torch::Tensor, 5> params_, m_, v_, grads_;
@@ -286,5 +289,38 @@ torch::Tensor knn_mean_distances(const torch::Tensor& positions, int k_neighbors
 ModelTensors init_gaussians_from_sparse(const torch::Tensor& positions, const torch::Tensor& colors, int sh_degree = 3,
                                         int k_neighbors = 3, int route = CUGS_KNN_AUTO,
                                         c10::optional<torch::Device> device = c10::nullopt);
+
+// Per-Gaussian contribution scores and score-based pruning (not in the reference).  The table is
+// [N,4] 32-bit words {sum of w, max of w, pixel count (uint32), padding} of the blend weight w = alpha T, zeroed at
+// construction and ADDED to by every launch (cugs_blend_scores): sums and counts add up over the views, the maximum is
+// the maximum over the views.
+struct ContributionScores {
+    ContributionScores(int64_t n, const torch::Device& device);
+    torch::Tensor table;                                   // [N,4] int32 words
+    int num_views = 0;
+    int64_t n() const { return table.size(0); }
+    torch::Tensor weight_sum() const;                      // [N] float32, a view of word 0
+    torch::Tensor weight_max() const;                      // [N] float32, a view of word 1
+    torch::Tensor pixel_count() const;                     // [N] int64, read from the uint32 word 2
+    void reset();
+};
+// One launch from an existing RenderOutput (its tile_ranges, gaussian_indices, packed records and tile_order); needs no
+// for_backward state.
+void accumulate_contribution_scores(ContributionScores& scores, const RenderOutput& render_out, const cugs_camera& camera);
+// Offline, over many views, with no colour blend: per view the projection at SH degree 0, the plain sort and the score
+// launch (one host sync per view: the sort's pair count).
+ContributionScores contribution_scores(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                                       const RenderSettings& settings = {});
+// Removes the rows whose entry of `prune_mask` (bool [N] on the model's device) is set, through cugs_densify_plan /
+// cugs_densify_apply (flag 4 = keep on the rows that stay): the survivors keep their relative order and their bits.  With `optimizer` its
+// parameter tensors are re-pointed at the new model, its moments carried over and its pending gradients cleared.
+// Returns the number removed.  Per-Gaussian state held elsewhere is the caller's: a DensificationController's
+// accumulators (the next accumulate_gradients or densify resizes them) and whatever an MCMCController keeps.
+int64_t prune_gaussians(ModelTensors& model, const torch::Tensor& prune_mask, FusedAdam* optimizer = nullptr);
+// The mask is weight_max < min_max_weight (when >= 0) and / or everything outside the round(keep_fraction N) largest
+// weight_sum (libtorch topk; when >= 0); both given: the union of the two prunes.  A Gaussian with weight_max == 0 is
+// always dropped.  Returns the number removed.
+int64_t prune_by_scores(ModelTensors& model, const ContributionScores& scores, float min_max_weight = -1.0f,
+                        float keep_fraction = -1.0f, FusedAdam* optimizer = nullptr);
 
 }  // namespace cugs_hip

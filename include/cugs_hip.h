@@ -253,6 +253,27 @@ int cugs_rasterize_forward_opts(int width, int height, const float background_ho
                                 float* out_color, float* out_final_T, int32_t* out_n_contrib,
                                 const cugs_blend_forward_opts* opts, void* stream);
 
+/* ---- per-Gaussian contribution scores (not in the reference) ---------
+ * The forward blend's walk without its colour: for every Gaussian g, statistics of its blend weight w = alpha * T over
+ * the pixels of this view, with the forward's decisions and the forward's w, bit for bit.  They are ADDED to row g of
+ * `scores`, a table [n,4] of 32-bit words, 16-byte aligned:
+ *   word 0  float   sum of w                       (float atomic adds: the last bits depend on their order)
+ *   word 1  float   largest w on any pixel         (exact: an unsigned atomic max on the bits, w >= 0)
+ *   word 2  uint32  number of pixels with w > 0    (exact; wraps at 2^32)
+ *   word 3  padding, never written
+ * The table is never cleared by the call: zero it once, then score V views with V calls - the sums and counts add up,
+ * the maximum is the maximum over the views.  A zeroed table is the identity of all three.
+ * Inputs as for cugs_rasterize_forward (no colour is read: there is no rgb, and of `packed` only the first 32 bytes of
+ * a record); tile_order as cugs_blend_forward_opts::tile_order (NULL: the spatial order).  gaussian_indices and the
+ * per-Gaussian sources may be NULL when every tile range is empty.
+ * CUGS_EINVAL for a negative size, a NULL `scores` with n > 0, gaussian_indices without a source (packed, or the three
+ * arrays), a NULL tile_ranges when something would be launched; CUGS_EALIGN for packed, tile_order or scores not
+ * 16-byte aligned; all before anything is queued.  n == 0 or an empty image: 0, nothing is launched.  Stream-ordered,
+ * no host sync, no workspace. */
+int cugs_blend_scores(int width, int height, const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                      const float* means_2d, const float* cov_2d_inv, const float* opacities_act,
+                      const float* packed, const void* tile_order, int n, void* scores, void* stream);
+
 /* ---- a7: rasterize_backward (backward.cu:239-306, kernel :31-233) -------------------
  * grad_accum: [n,CUGS_GRAD_STRIDE] floats, 64-byte aligned scratch (zeroed by the callee).  A row is
  *   {dL_drgb[3], dL_dopacity_act, M1x, M1y, M2xx, M2xy, M2yy, dL_dz, abs_x, abs_y, 0...}
