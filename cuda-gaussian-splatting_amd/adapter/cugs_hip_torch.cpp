@@ -46,8 +46,14 @@ torch::Tensor workspace(const torch::Device& dev, size_t bytes, int kind) {     
     // HIP caching allocator has gone away
     static thread_local auto& pool = *new std::vector<std::tuple<torch::Device, void*, int, torch::Tensor>>();
     void* st = static_cast<void*>(c10::hip::getCurrentHIPStream(dev.index()).stream());
-    auto make = [&] { return torch::empty({static_cast<int64_t>(bytes + bytes / 4 + 4096)},
-                                          torch::TensorOptions().dtype(torch::kUInt8).device(dev)); };
+    // the head of a NEW buffer is cleared: the sort's control words carry over from launch to launch, and a recycled
+    // block's garbage in the range flag would read as "a depth outside the fast range" (include/cugs_hip.h)
+    auto make = [&] {
+        auto t = torch::empty({static_cast<int64_t>(bytes + bytes / 4 + 4096)},
+                              torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+        t.slice(0, 0, 256).zero_();
+        return t;
+    };
     for (auto& e : pool)
         if (std::get<0>(e) == dev && std::get<1>(e) == st && std::get<2>(e) == kind) {
             if (static_cast<size_t>(std::get<3>(e).numel()) < bytes) std::get<3>(e) = make();

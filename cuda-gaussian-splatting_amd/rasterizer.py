@@ -50,6 +50,7 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
 # (cugs_project_forward_keyed writes the sort keys into it) nor steer each other's predictions.  The library itself
 # keeps no state; this is the caller-owned scratch of include/cugs_hip.h, one set per stream that renders.
 _workspaces: Dict[tuple, torch.Tensor] = {}
+SORT_CONTROL_BYTES = 256            # head of the N-level sort workspace: zero before its first use
 
 
 def _skey(device: torch.device) -> tuple:
@@ -95,6 +96,10 @@ def _workspace(device: torch.device, nbytes: int, kind: str = "n") -> torch.Tens
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=device)
+        # the sort's control words carry over from one launch to the next (include/cugs_hip.h: the first 256 bytes of a
+        # NEW N-level workspace must be zero) - a recycled block's garbage in the range flag reads as "a depth outside
+        # the fast range": a spurious -1 and WIDE_DEPTH_HOLD sorts on the general route every time the buffer grows
+        ws[:SORT_CONTROL_BYTES].zero_()
         _workspaces[key] = ws
     return ws
 
@@ -688,9 +693,14 @@ def render(model: GaussianModel, camera: CameraInfo, settings: RenderSettings, f
                             torch.empty((0, 2), **i),
                             depth_map=torch.zeros((camera.height, camera.width), **f) if want_depth_map else None)
     active_degree = min(int(settings.active_sh_degree), model.max_sh_degree())
+    # the sort below is the next user of this stream's sort workspace, and it consumes the projection's keys only on the
+    # narrow depth route: while the stream is in the wide-depth hold the general route rebuilds its keys from the arrays
+    # and never reads (or clears) the range flag a keyed projection of an out-of-range view raises - left standing, it
+    # would fail the probe of the narrow route when the hold runs out
+    wide = _wide_depth.get(_skey(dev), 0) > 0
     proj = project_gaussians(model.positions, model.rotations, model.scales, model.opacities, model.sh_coeffs,
                              camera, active_degree, settings.scale_modifier, want_colour_gate=for_backward,
-                             key_sort=True,       # the sort below is the next user of this stream's sort workspace
+                             key_sort=not wide,
                              colour_on_side_stream=OVERLAP_COLOUR)   # the SH stream travels underneath the sort
     # the backward blend's accumulator, cleared in passing by the forward blend (which leaves HBM idle)
     accum = torch.empty((n, _lib.GRAD_STRIDE), **f) if for_backward else None

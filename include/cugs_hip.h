@@ -76,7 +76,15 @@ int cugs_project_forward(int64_t n, int num_coeffs, int active_degree,
  * in `sort_workspace` (the N-level buffer, cugs_sort_workspace_bytes(n)), while they are in registers.  Not in the
  * reference, whose render() (rasterizer.cpp:58-75) hands the arrays from one stage to the next; this is what a
  * render() built on this library calls, followed by cugs_sort_pairs_predicted_keyed on the same stream with the same
- * workspace and camera size.  All outputs of cugs_project_forward are written as well, bit for bit. */
+ * workspace and camera size.  All outputs of cugs_project_forward are written as well, bit for bit.
+ * CONTRACT: a keyed projection must be consumed by a NARROW sort of the same workspace (cugs_sort_pairs_predicted_keyed
+ * / _keyed_ordered; cugs_sort_count_pairs and cugs_sort_pairs_predicted consume it too).  A view with a pair-emitting
+ * splat outside the narrow depth range raises the workspace's range flag here, and only a narrow sort reads and
+ * re-arms it: the *_wide entry points rebuild their keys from the arrays and neither read nor clear it.  Followed by a
+ * *_wide sort instead, the flag stays up and the NEXT narrow sort of that workspace reports -1 for a view that is in
+ * range (results stay correct - the caller re-sorts on the general route - but a host that keeps a sticky "wide" bit
+ * then spends another hold on the slow route).  A host that knows its next sort is a *_wide one calls
+ * cugs_project_forward instead (render() does: key the sort iff the stream is not in its wide-depth hold). */
 int cugs_project_forward_keyed(int64_t n, int num_coeffs, int active_degree,
                                const float* positions, const float* rotations, const float* scales,
                                const float* opacities, const float* sh_coeffs,
@@ -128,7 +136,11 @@ int cugs_pack_projected(int64_t n, const float* means_2d, const float* cov_2d_in
  * state from cugs_sort_count_pairs to cugs_sort_pairs and must be the same buffer in both calls,
  * with the same per-Gaussian inputs; `pair_workspace` (cugs_sort_pair_workspace_bytes(P)) can
  * only be sized after the count.  Size of the N-level buffer: ~59 bytes per Gaussian + 0.2 MB, and - up to 2 M
- * Gaussians - 40 KB per 4096 Gaussians more for the table of the keyed route's pair binning (69 MB in all at 1 M). */
+ * Gaussians - 40 KB per 4096 Gaussians more for the table of the keyed route's pair binning (69 MB in all at 1 M).
+ * The first 256 bytes of the N-level buffer are control words that carry over from one launch to the next (the range
+ * flag above among them): they must be ZERO when a newly allocated buffer is first used - garbage there reads as "a
+ * depth outside the narrow range" (a spurious -1 / a spurious repeat on the general route).  The library re-arms them
+ * itself from then on; the rest of the buffer, and the pair-level buffer, need no initialisation. */
 size_t cugs_sort_workspace_bytes(int64_t n);
 size_t cugs_sort_pair_workspace_bytes(int64_t total_pairs);
 
