@@ -132,6 +132,7 @@ SIGNATURES = {
     "cugs_adam_bias_correction": (None, [_F, _F, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cugs_fused_adam": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P]),
     "cugs_fused_adam_groups": (_I, [C.POINTER(AdamGroup), _I, _F, _F, _F, _F, _F, _P]),
+    "cugs_fused_adam_groups_rows": (_I, [C.POINTER(AdamGroup), _I, C.POINTER(C.c_int32), _P, _L, _F, _F, _F, _F, _F, _P]),
     "cugs_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_combined_loss": (_I, [_I, _I, _P, _P, _F, _I, _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_loss_opts_workspace_bytes": (C.c_size_t, [_I, _I]),
@@ -160,6 +161,10 @@ SIGNATURES = {
     "cugs_project_backward_adam_mcmc_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
                                                   C.POINTER(AdamFused), C.POINTER(McmcFused), _P, C.POINTER(PoseGrad),
                                                   _P]),
+    "cugs_project_backward_adam_sparse": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
+                                               C.POINTER(AdamFused), _P, _P]),
+    "cugs_project_backward_adam_sparse_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
+                                                    C.POINTER(AdamFused), _P, C.POINTER(PoseGrad), _P]),
     "cugs_ply_vertex_floats": (_I, [_I, _I]),
     "cugs_ply_pack": (_I, [_L, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     "cugs_ply_unpack": (_I, [_L, _I, _I, _P, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),

@@ -500,9 +500,14 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& ro, const ModelTensors& model,
                                const cugs_camera& camera, const RenderSettings& settings, FusedAdam* fused,
                                const MCMCController* mcmc, int step, const torch::Tensor& dL_ddepth_map,
-                               const torch::Tensor& dL_dalpha, bool want_camera_grad, bool want_abs_grad) {
+                               const torch::Tensor& dL_dalpha, bool want_camera_grad, bool want_abs_grad,
+                               bool sparse_adam) {
     TORCH_CHECK(!mcmc || fused, "the fused MCMC route needs the FusedAdam (otherwise: compute_regularization, step, "
                 "inject_noise)");
+    TORCH_CHECK(!sparse_adam || fused, "sparse_adam needs the FusedAdam (otherwise: render_backward, apply_gradients, "
+                "step(radii))");
+    TORCH_CHECK(!sparse_adam || !mcmc, "sparse_adam cannot be combined with the fused MCMC route: its regulariser and "
+                "noise act on every Gaussian");
     TORCH_CHECK(dL_dcolor.is_cuda(), "dL_dcolor must be on CUDA device");                             // rasterizer.cpp:122-124
     TORCH_CHECK(dL_dcolor.dim() == 3 && dL_dcolor.size(2) == 3, "dL_dcolor must be [H, W, 3]");
     TORCH_CHECK(!dL_ddepth_map.defined() || ro.depth_map.defined(),
@@ -577,6 +582,27 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                                                   &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam, &mc,
                                                   ptr<float>(o.dL_dmeans_2d), stream_of(dL_dcolor)),
                   "cugs_project_backward_adam_mcmc");
+            return o;
+        }
+        if (sparse_adam) {                                      // only the Gaussians this view sees
+            if (want_camera_grad) {
+                check(cugs_project_backward_adam_sparse_pose(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
+                                                             ptr<float>(model.positions), ptr<float>(model.rotations),
+                                                             ptr<float>(model.scales), ptr<float>(model.opacities),
+                                                             ptr<float>(model.sh_coeffs), ptr<int32_t>(radii),
+                                                             ptr<uint8_t>(gate), &camera, settings.scale_modifier,
+                                                             ptr<float>(rb.grad_accum), &adam, ptr<float>(o.dL_dmeans_2d),
+                                                             &pose, stream_of(dL_dcolor)),
+                      "cugs_project_backward_adam_sparse_pose");
+                return o;
+            }
+            check(cugs_project_backward_adam_sparse(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
+                                                    ptr<float>(model.positions), ptr<float>(model.rotations),
+                                                    ptr<float>(model.scales), ptr<float>(model.opacities),
+                                                    ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate),
+                                                    &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam,
+                                                    ptr<float>(o.dL_dmeans_2d), stream_of(dL_dcolor)),
+                  "cugs_project_backward_adam_sparse");
             return o;
         }
         if (want_camera_grad) {
@@ -713,7 +739,19 @@ cugs_adam_fused FusedAdam::begin_fused_step() {
     zero_grad();
     return a;
 }
-void FusedAdam::step() {
+void FusedAdam::step() { step_groups(nullptr); }
+void FusedAdam::step(const torch::Tensor& visible) {
+    const int64_t n_rows = params_[0].size(0);
+    TORCH_CHECK(visible.defined() && visible.dim() == 1 && visible.size(0) == n_rows,
+                "FusedAdam: visible must be a [N] tensor with N = ", n_rows, " (RenderOutput::radii or a bool mask)");
+    TORCH_CHECK(visible.is_cuda() && visible.device() == params_[0].device(),
+                "FusedAdam: visible must be on the model's CUDA device");
+    TORCH_CHECK(visible.scalar_type() == torch::kInt32 || visible.scalar_type() == torch::kBool,
+                "FusedAdam: visible must be int32 radii or a bool mask, got ", visible.dtype());
+    const torch::Tensor rows = (visible.scalar_type() == torch::kBool ? visible.to(torch::kInt32) : visible).contiguous();
+    step_groups(&rows);
+}
+void FusedAdam::step_groups(const torch::Tensor* rows) {
     ++step_count_;
     float bc1, bc2;
     cugs_adam_bias_correction(h_.beta1, h_.beta2, step_count_, &bc1, &bc2);
@@ -732,7 +770,19 @@ void FusedAdam::step() {
         groups[i].m = mc[i].data_ptr<float>(); groups[i].v = vc[i].data_ptr<float>(); groups[i].n = pc[i].numel();
         st = stream_of(params_[i]);
     }
-    check(cugs_fused_adam_groups(groups, 5, h_.beta1, h_.beta2, h_.eps, bc1, bc2, st), "cugs_fused_adam_groups");
+    if (rows) {
+        const int64_t n_rows = rows->size(0);
+        int32_t row_elems[5];
+        for (int i = 0; i < 5; ++i) {                             // floats per row: 3, 3C, 1, 3, 4
+            int64_t w = 1;
+            for (int64_t d = 1; d < params_[i].dim(); ++d) w *= params_[i].size(d);
+            row_elems[i] = static_cast<int32_t>(w);
+        }
+        check(cugs_fused_adam_groups_rows(groups, 5, row_elems, rows->data_ptr<int32_t>(), n_rows, h_.beta1, h_.beta2,
+                                          h_.eps, bc1, bc2, st), "cugs_fused_adam_groups_rows");
+    } else {
+        check(cugs_fused_adam_groups(groups, 5, h_.beta1, h_.beta2, h_.eps, bc1, bc2, st), "cugs_fused_adam_groups");
+    }
     for (int i = 0; i < 5; ++i) {                                 // fused_adam.cu:216-218
         if (!grads_[i].defined()) continue;
         if (!params_[i].is_contiguous()) params_[i].copy_(pc[i]);

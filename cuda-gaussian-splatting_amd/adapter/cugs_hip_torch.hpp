@@ -124,7 +124,11 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                                const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
                                FusedAdam* fused = nullptr, const MCMCController* mcmc = nullptr, int step = 0,
                                const torch::Tensor& dL_ddepth_map = {}, const torch::Tensor& dL_dalpha = {},
-                               bool want_camera_grad = false, bool want_abs_grad = false);
+                               bool want_camera_grad = false, bool want_abs_grad = false, bool sparse_adam = false);
+// `sparse_adam` (with `fused` only, never with `mcmc`; not in the reference): the fused step touches only
+// the Gaussians this view sees, render_out.radii > 0 (cugs_project_backward_adam_sparse / _sparse_pose) - bit for bit
+// render_backward + apply_gradients + step(render_out.radii); every other Gaussian keeps parameters and moments and is
+// not read at all.
 // `mcmc` (with `fused` only): the regulariser gradient and the position noise of iteration `step` ride in
 // the same launch (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + compute_regularization's
 // gradients, apply_gradients, step, inject_noise(model, step).
@@ -166,6 +170,11 @@ public:
     void set_lr(int group, float lr) { lrs_[group] = lr; }
     float get_lr(int group) const { return lrs_[group]; }
     void step();
+    // Sparse Adam (not in the reference): `visible` is RenderOutput::radii of the view just rendered
+    // (int32 [N]) or a bool [N] mask; only the rows with radii > 0 are stepped, exactly as step() would step them (bias
+    // corrections from the global step count, which advances by one whatever the mask); the others keep parameters and
+    // moments bit for bit and are neither read nor written (cugs_fused_adam_groups_rows).
+    void step(const torch::Tensor& visible);
     // The optimizer half of cugs_project_backward_adam: counts the step, returns moments / learning rates / bias
     // corrections for the launch that updates the parameters in place (they must be contiguous float32).
     cugs_adam_fused begin_fused_step();
@@ -178,6 +187,7 @@ private:
     friend int64_t prune_gaussians(ModelTensors&, const torch::Tensor&, FusedAdam*);   // carries m_/v_ through the prune
     friend bool write_gaussian_ply(const std::string&, const ModelTensors&, const FusedAdam*);
     friend ModelTensors read_gaussian_ply(const std::string&, const torch::Device&, FusedAdam*);
+    void step_groups(const torch::Tensor* rows);     // rows: int32 [N] radii of the sparse step, or nullptr
     std::array<torch::Tensor, 5> params_, m_, v_, grads_;
     std::array<float, 5> lrs_;
     AdamHyper h_;

@@ -2,7 +2,8 @@
 // it) and the fused Adam route's argument checks, shared by two translation units: project_backward.hip (every entry
 // point without MCMC) and project_backward_mcmc.hip (cugs_project_backward_adam_mcmc, N5).  The MCMC instantiations
 // of k_project_backward live in the second one: compiled into the same module they changed the register allocation
-// of the existing ADAM instantiations; apart, those compile to the same code as without N5.
+// of the existing ADAM instantiations; apart, those compile to the same code as without N5.  The POSE instantiations
+// (project_backward_pose.hip) and the SPARSE ones (project_backward_sparse.hip) are kept apart in the same way.
 #pragma once
 #include "cugs_raster_common.h"
 #include "cugs_mcmc.h"
@@ -145,13 +146,48 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
 }
 // The workgroup's SH gradient tile (LDS, padded rows) applied to its contiguous chunk of coefficients, moments
 // read and written as 16-byte streams: the 12C B/Gaussian gradient never goes to memory.
-template <int C, bool ALIGNED>
+// SPARSE: s_vis[r] != 0 marks the rows that are stepped.  A 16-byte piece none of whose rows is marked is
+// neither loaded nor stored; a piece that straddles a marked and an unmarked row (3C is no multiple of four floats) is
+// loaded, updated in its marked elements only and stored whole by the one thread that owns it.
+template <int C, bool ALIGNED, bool SPARSE = false>
 __device__ __forceinline__ void adam_sh_rows(float* __restrict__ param, float* __restrict__ mom, float* __restrict__ var,
-                                             int64_t base, int count, const float* s_sh, float lr, const AdamFusedArgs& h) {
+                                             int64_t base, int count, const float* s_sh, float lr, const AdamFusedArgs& h,
+                                             const float* s_vis = nullptr) {
     constexpr int ROW = ShTile<C>::ROW, LROW = ShTile<C>::LROW;
     float* P = param + base * ROW; float* M = mom + base * ROW; float* V = var + base * ROW;
     const int total = count * ROW;
     int done = 0;
+    if constexpr (SPARSE) {
+        if (ALIGNED) {
+            const int total4 = total >> 2;
+            for (int e4 = threadIdx.x; e4 < total4; e4 += CUGS_BLOCK) {
+                int e = e4 * 4, row = e / ROW, col = e - row * ROW;
+                float g[4];
+                bool vis[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {                              // e + k < total: row < count
+                    g[k] = s_sh[row * LROW + col];
+                    vis[k] = s_vis[row] != 0.0f;
+                    if (++col == ROW) { col = 0; ++row; }
+                }
+                if (!(vis[0] || vis[1] || vis[2] || vis[3])) continue;     // nothing of this piece is read or written
+                float4 pp = cugs_ldnt(reinterpret_cast<float4*>(P) + e4), mm = cugs_ldnt(reinterpret_cast<float4*>(M) + e4),
+                       vv = cugs_ldnt(reinterpret_cast<float4*>(V) + e4);
+                if (vis[0]) adam_update(pp.x, g[0], mm.x, vv.x, lr, h);
+                if (vis[1]) adam_update(pp.y, g[1], mm.y, vv.y, lr, h);
+                if (vis[2]) adam_update(pp.z, g[2], mm.z, vv.z, lr, h);
+                if (vis[3]) adam_update(pp.w, g[3], mm.w, vv.w, lr, h);
+                cugs_stnt(reinterpret_cast<float4*>(P) + e4, pp); cugs_stnt(reinterpret_cast<float4*>(M) + e4, mm);
+                cugs_stnt(reinterpret_cast<float4*>(V) + e4, vv);
+            }
+            done = total4 << 2;
+        }
+        for (int e = done + threadIdx.x; e < total; e += CUGS_BLOCK) {
+            int row = e / ROW, col = e - row * ROW;
+            if (s_vis[row] != 0.0f) adam_update(P[e], s_sh[row * LROW + col], M[e], V[e], lr, h);
+        }
+        return;
+    }
     if (ALIGNED) {
         const int total4 = total >> 2;
         for (int e4 = threadIdx.x; e4 < total4; e4 += CUGS_BLOCK) {
@@ -180,6 +216,9 @@ __device__ __forceinline__ void adam_sh_rows(float* __restrict__ param, float* _
 // adam_sh_rows with the gradient formed from the factor tile (store_sh_rows_from_factors): the same products, the same
 // update, in batches of four 16-byte pieces per thread so that a workgroup's 36 loads per thread are not twelve
 // dependent round trips.
+// SPARSE: word 19 of a factor row (row[4].w) is the row's visibility flag; a row is twelve whole pieces, so
+// a piece is stepped or left alone as a whole, and the batched loads of a skipped piece are not issued either.
+template <bool SPARSE = false>
 __device__ __forceinline__ void adam_sh_rows_from_factors(float* __restrict__ param, float* __restrict__ mom, float* __restrict__ var,
                                                           int64_t base, int count, int num_active, const float* s_fac,
                                                           float lr, const AdamFusedArgs& h) {
@@ -188,6 +227,35 @@ __device__ __forceinline__ void adam_sh_rows_from_factors(float* __restrict__ pa
     float4* M = reinterpret_cast<float4*>(mom + base * (3 * C));
     float4* V = reinterpret_cast<float4*>(var + base * (3 * C));
     const int total4 = count * ROW4;
+    if constexpr (SPARSE) {
+#pragma unroll
+        for (int b = 0; b < ROW4; b += BATCH) {
+            float4 pp[BATCH], mm[BATCH], vv[BATCH];
+            bool on[BATCH];
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u) {
+                const int e4 = (int)threadIdx.x + (b + u) * CUGS_BLOCK;
+                on[u] = e4 < total4 && s_fac[(e4 / ROW4) * SH_FACTOR_ROW + 19] != 0.0f;
+                pp[u] = mm[u] = vv[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (on[u]) { pp[u] = cugs_ldnt(P + e4); mm[u] = cugs_ldnt(M + e4); vv[u] = cugs_ldnt(V + e4); }
+            }
+#pragma unroll
+            for (int u = 0; u < BATCH; ++u) {
+                const int e4 = (int)threadIdx.x + (b + u) * CUGS_BLOCK;
+                if (on[u]) {
+                    const int r = e4 / ROW4, j = e4 - r * ROW4, ch = j >> 2, k = (j & 3) * 4;
+                    const float4 y = *reinterpret_cast<const float4*>(s_fac + r * SH_FACTOR_ROW + k);
+                    const float g = s_fac[r * SH_FACTOR_ROW + 16 + ch];
+                    adam_update(pp[u].x, k + 0 < num_active ? g * y.x : 0.0f, mm[u].x, vv[u].x, lr, h);
+                    adam_update(pp[u].y, k + 1 < num_active ? g * y.y : 0.0f, mm[u].y, vv[u].y, lr, h);
+                    adam_update(pp[u].z, k + 2 < num_active ? g * y.z : 0.0f, mm[u].z, vv[u].z, lr, h);
+                    adam_update(pp[u].w, k + 3 < num_active ? g * y.w : 0.0f, mm[u].w, vv[u].w, lr, h);
+                    cugs_stnt(P + e4, pp[u]); cugs_stnt(M + e4, mm[u]); cugs_stnt(V + e4, vv[u]);
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int b = 0; b < ROW4; b += BATCH) {
         float4 pp[BATCH], mm[BATCH], vv[BATCH];
@@ -344,13 +412,20 @@ __device__ __forceinline__ void pose_block_partial(const float (&v)[POSE_TERMS],
 // J^T K and dL/dtvec = dt (zeros where the geometry branch does not run), and the workgroup writes their sum to
 // pose.partial[blockIdx.x] (pose_block_partial); pose.rows, when given, receives each Gaussian's twelve terms.  Dead
 // lanes stay to the end for the workgroup's barriers.  Everything else it computes is what the variant without it does.
-template <int C, bool ALIGNED, bool ADAM, bool FACTORS = false, bool MCMC = false, bool POSE = false>
+// SPARSE (with ADAM, never MCMC; project_backward_sparse.hip): only the Gaussians the view sees
+// (radii > 0) are stepped, exactly as the dense route steps them.  A thread whose radius is 0 reads no gradient row and
+// no geometry, runs none of its eleven adam_update triples, marks its SH row as skipped for the cooperative update,
+// writes (0, 0) to d_means_out, adds zeros to the camera terms and stays for the barriers.
+template <int C, bool ALIGNED, bool ADAM, bool FACTORS = false, bool MCMC = false, bool POSE = false, bool SPARSE = false>
 __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int degree, CamArgs cam, PBPtrs p,
                                                                 AdamFusedArgs adam, McmcFusedArgs mc, PoseArgs pose) {
     static_assert(!MCMC || ADAM, "the MCMC route is the fused optimizer step's");
     static_assert(!FACTORS || (C == 16 && ALIGNED), "factor tile: degree-3 storage, 16-byte rows");
+    static_assert(!SPARSE || (ADAM && !MCMC), "the sparse route is the fused optimizer step's, and not MCMC's");
     constexpr int LROW = FACTORS ? SH_FACTOR_ROW : ShTile<C>::LROW;
-    __shared__ __attribute__((aligned(16))) float s_sh[CUGS_BLOCK * LROW];
+    // SPARSE on the plain tile: one visibility flag per row behind the tile (the factor tile has a free word per row)
+    constexpr int VIS_WORDS = (SPARSE && !FACTORS) ? CUGS_BLOCK : 0;
+    __shared__ __attribute__((aligned(16))) float s_sh[CUGS_BLOCK * LROW + VIS_WORDS];
     const int64_t base = (int64_t)blockIdx.x * CUGS_BLOCK;
     const int count = (int)min((int64_t)CUGS_BLOCK, n - base);
     const int64_t idx = base + threadIdx.x;
@@ -380,11 +455,17 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
     int in_radius = 0;
     if (FACTORS && live) {
         in_radius = p.radii[idx];
-        in_scl[0] = ldp(p.scales + idx * 3 + 0); in_scl[1] = ldp(p.scales + idx * 3 + 1); in_scl[2] = ldp(p.scales + idx * 3 + 2);
-        in_q = ADAM ? reinterpret_cast<const float4*>(p.rotations)[idx] : cugs_ldnt(reinterpret_cast<const float4*>(p.rotations) + idx);
-        in_opa = ldp(p.opacities + idx);
+        if (!SPARSE || in_radius > 0) {
+            in_scl[0] = ldp(p.scales + idx * 3 + 0); in_scl[1] = ldp(p.scales + idx * 3 + 1); in_scl[2] = ldp(p.scales + idx * 3 + 2);
+            in_q = ADAM ? reinterpret_cast<const float4*>(p.rotations)[idx] : cugs_ldnt(reinterpret_cast<const float4*>(p.rotations) + idx);
+            in_opa = ldp(p.opacities + idx);
+        }
     }
-    if (live) {
+    if constexpr (SPARSE && !FACTORS) {
+        if (live) in_radius = p.radii[idx];
+    }
+    const bool work = SPARSE ? (live && in_radius > 0) : live;       // SPARSE: an unseen row is not read at all
+    if (work) {
         pos = V3{ldp(p.positions + idx * 3 + 0), ldp(p.positions + idx * 3 + 1), ldp(p.positions + idx * 3 + 2)};
         float g_rgb[3];
         if (from_rows) {
@@ -416,20 +497,25 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
         // kernel-uniform: without dL/dsh (the data-parallel exchange builds it from the gathered colour gradients,
         // cugs_sh_backward_views) nothing goes through the tile
         if (ADAM || p.d_sh) {
-            if (live) {
+            if (work) {
                 float4* row = reinterpret_cast<float4*>(s_sh + threadIdx.x * SH_FACTOR_ROW);
                 row[0] = make_float4(Y[0], Y[1], Y[2], Y[3]);
                 row[1] = make_float4(Y[4], Y[5], Y[6], Y[7]);
                 row[2] = make_float4(Y[8], Y[9], Y[10], Y[11]);
                 row[3] = make_float4(Y[12], Y[13], Y[14], Y[15]);
-                row[4] = make_float4(gated[0], gated[1], gated[2], 0.0f);
+                row[4] = make_float4(gated[0], gated[1], gated[2], SPARSE ? 1.0f : 0.0f);
+            } else if constexpr (SPARSE) {
+                if (live) reinterpret_cast<float4*>(s_sh + threadIdx.x * SH_FACTOR_ROW)[4] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
             __syncthreads();
-            if (ADAM) adam_sh_rows_from_factors(p.w_sh, adam.m[1], adam.v[1], base, count, num_active, s_sh, adam.lr[1], adam);
+            if (ADAM) adam_sh_rows_from_factors<SPARSE>(p.w_sh, adam.m[1], adam.v[1], base, count, num_active, s_sh, adam.lr[1], adam);
             else store_sh_rows_from_factors(p.d_sh, base, count, num_active, s_sh);
         }
     } else if (ADAM || p.d_sh) {                               // kernel-uniform
-        if (live) {
+        if constexpr (SPARSE) {
+            if (live) s_sh[CUGS_BLOCK * LROW + threadIdx.x] = work ? 1.0f : 0.0f;
+        }
+        if (work) {
             float* row = s_sh + threadIdx.x * LROW;
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch)
@@ -437,7 +523,8 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
                 for (int k = 0; k < C; ++k) row[ch * C + k] = (k < num_active) ? gated[ch] * Y[k] : 0.0f;
         }
         __syncthreads();
-        if (ADAM) adam_sh_rows<C, ALIGNED>(p.w_sh, adam.m[1], adam.v[1], base, count, s_sh, adam.lr[1], adam);
+        if (ADAM) adam_sh_rows<C, ALIGNED, SPARSE>(p.w_sh, adam.m[1], adam.v[1], base, count, s_sh, adam.lr[1], adam,
+                                                   s_sh + CUGS_BLOCK * LROW);
         else store_sh_rows<C, ALIGNED>(p.d_sh, base, count, s_sh);
     }
     if (!POSE && !live) return;
@@ -445,12 +532,12 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
 #pragma unroll
     for (int k = 0; k < POSE_TERMS; ++k) pg[k] = 0.0f;
 
-    if (live) {
+    if (work) {
         // ---- geometry ----
         V3 d_pos{0.0f, 0.0f, 0.0f}, d_log{0.0f, 0.0f, 0.0f};
         float4 d_q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         float d_logit = 0.0f;
-        if ((FACTORS ? in_radius : p.radii[idx]) > 0) {            // projection_backward.cu:48
+        if (((FACTORS || SPARSE) ? in_radius : p.radii[idx]) > 0) {   // projection_backward.cu:48
             const M3 W = view_rotation(cam);
             const V3 t = to_camera(cam, W, pos);
             if (!FACTORS) {
@@ -581,6 +668,8 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_project_backward(int64_t n, int 
             cugs_stnt(p.d_opa + idx, d_logit);
         }
         if (p.d_means_out) { p.d_means_out[idx * 2 + 0] = g_mx; p.d_means_out[idx * 2 + 1] = g_my; }
+    } else if constexpr (SPARSE) {
+        if (live && p.d_means_out) { p.d_means_out[idx * 2 + 0] = 0.0f; p.d_means_out[idx * 2 + 1] = 0.0f; }   // as the dense route
     }
     if constexpr (POSE) {
         if (live && pose.rows) {

@@ -127,7 +127,29 @@ class FusedAdam:
         self.grads_ = [None] * self.kNumGroups
         return a
 
-    def step(self) -> None:
+    def step(self, visible: Optional[torch.Tensor] = None) -> None:
+        """One Adam step over the groups that have a gradient.
+        `visible` (optional, not in the reference): sparse Adam - RenderOutput.radii of the view just
+        rendered (int32 [N]) or a bool [N] mask.  Only the rows with radii > 0 (True) are stepped, exactly as the dense
+        step would step them, with the bias corrections of the optimizer's global step count; the other rows keep
+        parameters and moments bit for bit and are neither read nor written (cugs_fused_adam_groups_rows).  The step
+        count advances by one whatever the mask.  A row first seen late, with zero moments, takes a first step of about
+        lr (1 - beta1) / sqrt(1 - beta2) = 3.2 lr.  None: the dense step."""
+        rows = None
+        if visible is not None:
+            n_rows = int(self.model_.positions.shape[0])
+            if not isinstance(visible, torch.Tensor) or visible.dim() != 1 or int(visible.shape[0]) != n_rows:
+                raise RuntimeError(f"FusedAdam: visible must be a [N] tensor with N = {n_rows} (RenderOutput.radii or a "
+                                   "bool mask)")
+            if not visible.is_cuda or visible.device != self.model_.positions.device:
+                raise RuntimeError("FusedAdam: visible must be on the model's CUDA device")
+            if visible.dtype == torch.bool:
+                rows = visible.to(torch.int32)
+            elif visible.dtype == torch.int32:
+                rows = visible
+            else:
+                raise RuntimeError(f"FusedAdam: visible must be int32 radii or a bool mask, got {visible.dtype}")
+            rows = rows.contiguous()
         self.step_count_ += 1
         bc1, bc2 = C.c_float(), C.c_float()
         lib.cugs_adam_bias_correction(self.config_.beta1, self.config_.beta2, self.step_count_,
@@ -164,8 +186,17 @@ class FusedAdam:
         if dev is None:
             return
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib.cugs_fused_adam_groups(groups, self.kNumGroups, self.config_.beta1, self.config_.beta2,
-                                         self.config_.eps, bc1.value, bc2.value, stream),
-              "cugs_fused_adam_groups")
+        if rows is not None:
+            n_rows = int(rows.shape[0])
+            row_elems = (C.c_int32 * self.kNumGroups)(
+                *[int(math.prod(getattr(self.model_, nm).shape[1:])) for nm in self._names])   # floats per row
+            check(lib.cugs_fused_adam_groups_rows(groups, self.kNumGroups, row_elems, C.c_void_p(rows.data_ptr()),
+                                                  n_rows, self.config_.beta1, self.config_.beta2, self.config_.eps,
+                                                  bc1.value, bc2.value, stream),
+                  "cugs_fused_adam_groups_rows")
+        else:
+            check(lib.cugs_fused_adam_groups(groups, self.kNumGroups, self.config_.beta1, self.config_.beta2,
+                                             self.config_.eps, bc1.value, bc2.value, stream),
+                  "cugs_fused_adam_groups")
         for dst, src in copy_back:                 # fused_adam.cu:216-218
             dst.copy_(src)

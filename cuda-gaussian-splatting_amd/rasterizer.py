@@ -735,7 +735,7 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                     mcmc=None, mcmc_step: int = 0, mcmc_noise: Optional[torch.Tensor] = None,
                     dL_ddepth_map: Optional[torch.Tensor] = None,
                     dL_dalpha: Optional[torch.Tensor] = None, want_camera_grad: bool = False,
-                    want_abs_grad: bool = False) -> BackwardOutput:
+                    want_abs_grad: bool = False, sparse_adam: bool = False) -> BackwardOutput:
     """`dL_drgb_gated_out` ([N,3], optional, not in the reference): when given, the per-view SH gradient
     is NOT materialised (dL_dsh_coeffs is None) and the gated colour gradient is written there instead,
     for parallel.exchange_gradients() to rebuild the summed SH gradient after the all-gather.
@@ -766,7 +766,19 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
     on every route (plain, fused_adam, mcmc, want_camera_grad, the depth / alpha map gradients, the data-parallel
     arguments).  It is an [N,2] float32 VIEW of the blend's accumulator rows (row stride 16 floats, no copy; it keeps
     the rows alive): pass it to DensificationController.accumulate_gradients as it is.  Every other output is the same
-    up to the order of the blend's atomic adds.  Without the flag the field is None and nothing changes."""
+    up to the order of the blend's atomic adds.  Without the flag the field is None and nothing changes.
+    `sparse_adam=True` (with fused_adam only, never with mcmc; not in the reference): the fused step
+    touches only the Gaussians this view sees, render_out.radii > 0 (cugs_project_backward_adam_sparse, with
+    want_camera_grad cugs_project_backward_adam_sparse_pose).  A visible Gaussian is stepped exactly as the dense fused
+    route steps it (bias corrections from the optimizer's global step count, which advances by one either way); every
+    other Gaussian keeps parameters and moments bit for bit and is not read at all.  Equivalent, bit for bit, to
+    render_backward + apply_gradients + step(visible=render_out.radii); dL_dmeans_2d, dL_dviewmat and dL_dmeans_2d_abs
+    are those of the dense fused route.  The depth / alpha map gradients and want_abs_grad work unchanged."""
+    _torch_check(not sparse_adam or fused_adam is not None,
+                 "sparse_adam needs fused_adam (otherwise: render_backward, apply_gradients, step(visible=radii))")
+    _torch_check(not sparse_adam or mcmc is None,
+                 "sparse_adam cannot be combined with the fused MCMC route: its regulariser and noise act on every "
+                 "Gaussian")
     _torch_check(dL_dcolor.is_cuda, "dL_dcolor must be on CUDA device")
     _torch_check(dL_dcolor.dim() == 3 and dL_dcolor.shape[2] == 3, "dL_dcolor must be [H, W, 3]")
     depth_grads = dL_ddepth_map is not None or dL_dalpha is not None
@@ -837,6 +849,12 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
             else:
                 check(lib.cugs_project_backward_adam_mcmc(*args, C.byref(mc), _ptr(d_means_2d), _stream(dev)),
                       "cugs_project_backward_adam_mcmc")
+        elif sparse_adam and pg is not None:
+            check(lib.cugs_project_backward_adam_sparse_pose(*args, _ptr(d_means_2d), C.byref(pg), _stream(dev)),
+                  "cugs_project_backward_adam_sparse_pose")
+        elif sparse_adam:
+            check(lib.cugs_project_backward_adam_sparse(*args, _ptr(d_means_2d), _stream(dev)),
+                  "cugs_project_backward_adam_sparse")
         elif pg is not None:
             check(lib.cugs_project_backward_adam_pose(*args, _ptr(d_means_2d), C.byref(pg), _stream(dev)),
                   "cugs_project_backward_adam_pose")

@@ -439,6 +439,28 @@ typedef struct cugs_adam_group {
 int cugs_fused_adam_groups(const cugs_adam_group* groups_host, int ngroups, float beta1,
                            float beta2, float eps, float bc1, float bc2, void* stream);
 
+/* ---- sparse Adam (not in the reference): step only the rows a view sees -------------------------
+ * cugs_fused_adam_groups_rows: cugs_fused_adam_groups restricted to the rows with radii[row] > 0 (radii: DEVICE int32
+ * [n_rows], cugs_project_forward's, of the view just rendered; a visible row whose gradient is zero is still stepped).
+ * Group k holds n_rows rows of row_elems_host[k] floats (3, 3 num_coeffs, 1, 3, 4 for the five model tensors).
+ *   visible row:    exactly cugs_fused_adam_groups' update - the same arithmetic in the same order, with the bc1 / bc2
+ *                   given (the optimizer's GLOBAL step count; Inria's sparse_adam and gsplat's SelectiveAdam apply no
+ *                   bias correction at all), so all rows visible = cugs_fused_adam_groups, bit for bit;
+ *   invisible row:  param, m and v keep their bits; nothing of the row is read or written, except that a 16-byte piece
+ *                   shared with a visible row is loaded and stored whole with the invisible elements unchanged.
+ * Hence for any mask: result = where(visible row, cugs_fused_adam_groups' result, value before), bit for bit.
+ * One launch; a group with grad == NULL is skipped.  CUGS_EINVAL: ngroups > 8, a group with row_elems <= 0 or
+ * n != row_elems * n_rows, radii == NULL with n_rows > 0; n_rows == 0 returns 0 and queues nothing.
+ * cugs_project_backward_adam_sparse / _sparse_pose: cugs_project_backward_adam / _adam_pose under the same rule, with
+ * the `radii` they are given anyway: a Gaussian with radii <= 0 is not read (no gradient row, no geometry, none of its
+ * parameter and moment words), dL_dmeans_2d_out gets (0, 0) for it and dL_dview nothing from it, as on the dense
+ * routes; every visible Gaussian is stepped exactly as the dense route steps it.  Same arguments, same checks, same
+ * error codes as the dense entry points.  There is no sparse MCMC route: its regulariser and noise act on every
+ * Gaussian. */
+int cugs_fused_adam_groups_rows(const cugs_adam_group* groups_host, int ngroups, const int32_t* row_elems_host,
+                                const int32_t* radii, int64_t n_rows, float beta1, float beta2, float eps,
+                                float bc1, float bc2, void* stream);
+
 /* ---- N1: combined_loss + dL/dcolor (training/loss.cpp:88-140, trainer.cpp:214-217) ----
  * L = (1-lambda) mean|x-y| + lambda (1 - mean SSIM), SSIM with a window_size x window_size sigma-1.5
  * Gaussian window (odd, 3..15; the reference default is 11), zero padding, C1 = 1e-4, C2 = 9e-4.
@@ -666,6 +688,20 @@ int cugs_project_backward_adam_mcmc_pose(int64_t n, int num_coeffs, int active_d
                                          const float* grad_accum, const cugs_adam_fused* adam_host,
                                          const cugs_mcmc_fused* mcmc_host, float* dL_dmeans_2d_out,
                                          const cugs_pose_grad* pose_host, void* stream);
+
+/* The fused routes of sparse Adam (semantics: the sparse Adam block beside cugs_fused_adam_groups_rows above). */
+int cugs_project_backward_adam_sparse(int64_t n, int num_coeffs, int active_degree, float* positions,
+                                      float* rotations, float* scales, float* opacities, float* sh_coeffs,
+                                      const int32_t* radii, const uint8_t* colour_gate,
+                                      const cugs_camera* camera_host, float scale_modifier,
+                                      const float* grad_accum, const cugs_adam_fused* adam_host,
+                                      float* dL_dmeans_2d_out, void* stream);
+int cugs_project_backward_adam_sparse_pose(int64_t n, int num_coeffs, int active_degree, float* positions,
+                                           float* rotations, float* scales, float* opacities, float* sh_coeffs,
+                                           const int32_t* radii, const uint8_t* colour_gate,
+                                           const cugs_camera* camera_host, float scale_modifier,
+                                           const float* grad_accum, const cugs_adam_fused* adam_host,
+                                           float* dL_dmeans_2d_out, const cugs_pose_grad* pose_host, void* stream);
 
 /* ---- init_gaussians_from_sparse (core/gaussian_init.cpp:25-152) on the device ----------------------------------
  * The reference turns a point cloud into a model on the CPU: positions copied, the DC coefficient from the colour
