@@ -79,6 +79,12 @@ class LossOpts(C.Structure):
     """struct cugs_loss_opts."""
     _fields_ = [("exposure", C.c_void_p), ("mask", C.c_void_p), ("dL_dexposure", C.c_void_p), ("corrected", C.c_void_p)]
 
+
+class DepthLossOpts(C.Structure):
+    """struct cugs_depth_loss_opts."""
+    _fields_ = [("weight", C.c_void_p), ("scale_shift", C.c_void_p), ("fit", C.c_int), ("inverse", C.c_int),
+                ("min_alpha", C.c_float), ("expected", C.c_void_p)]
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -137,6 +143,8 @@ SIGNATURES = {
     "cugs_combined_loss": (_I, [_I, _I, _P, _P, _F, _I, _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_loss_opts_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_combined_loss_opts": (_I, [_I, _I, _P, _P, _F, _I, C.POINTER(LossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
+    "cugs_depth_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "cugs_depth_loss": (_I, [_I, _I, _P, _P, _P, C.POINTER(DepthLossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_eval_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_eval_metrics": (_I, [_I, _I, _P, _P, _P, _I, _P, C.c_size_t, _P, _P]),
     "cugs_densify_accumulate": (_I, [_L, _P, _P, _P, _P, _P, _P]),

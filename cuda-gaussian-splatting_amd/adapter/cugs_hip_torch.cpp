@@ -717,6 +717,50 @@ ExposureLoss combined_loss_exposure(const torch::Tensor& rendered, const torch::
     return o;
 }
 
+DepthLoss depth_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha, const torch::Tensor& target,
+                     const torch::Tensor& weight, bool inverse, const torch::Tensor& align, bool fit, float min_alpha,
+                     bool want_grad, bool want_expected) {
+    TORCH_CHECK(depth_map.dim() == 2, "depth_map must be 2-dimensional [H, W], got ", depth_map.dim(), " dims");
+    TORCH_CHECK(depth_map.dtype() == torch::kFloat32, "depth_map must be float32, got ", depth_map.dtype());
+    TORCH_CHECK(depth_map.is_cuda(), "depth_map must be on a CUDA device");
+    const int h = static_cast<int>(depth_map.size(0)), w = static_cast<int>(depth_map.size(1));
+    auto validate_map = [&](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.dim() == 2 && t.size(0) == h && t.size(1) == w, name, " must be [H, W], got ", t.sizes());
+        TORCH_CHECK(t.dtype() == torch::kFloat32, name, " must be float32, got ", t.dtype());
+        TORCH_CHECK(t.is_cuda() && t.device() == depth_map.device(), name, " must be on the depth map's CUDA device");
+    };
+    validate_map(alpha, "alpha");
+    validate_map(target, "target");
+    torch::Tensor wt, ss;
+    if (weight.defined()) { validate_map(weight, "weight"); wt = weight.contiguous(); }
+    TORCH_CHECK(min_alpha > 0.0f && std::isfinite(min_alpha), "min_alpha must be positive and finite, got ", min_alpha);
+    TORCH_CHECK(!(fit && align.defined()), "align must be a fit or a given (s, b), not both");
+    if (align.defined()) {
+        TORCH_CHECK(align.dim() == 1 && align.size(0) == 2, "align must be [2] = (s, b), got ", align.sizes());
+        TORCH_CHECK(align.dtype() == torch::kFloat32, "align must be float32, got ", align.dtype());
+        TORCH_CHECK(align.is_cuda() && align.device() == depth_map.device(), "align must be on the depth map's CUDA device");
+        ss = align.contiguous();
+    }
+    auto d = depth_map.contiguous(), a = alpha.contiguous(), t = target.contiguous();
+    auto out = torch::empty({8}, fopt(depth_map));
+    DepthLoss o;
+    if (want_grad) { o.dL_ddepth_map = torch::empty({h, w}, fopt(depth_map)); o.dL_dalpha = torch::empty({h, w}, fopt(depth_map)); }
+    if (want_expected) o.expected = torch::empty({h, w}, fopt(depth_map));
+    cugs_depth_loss_opts opts{};
+    opts.weight = ptr<float>(wt);
+    opts.scale_shift = ptr<float>(ss);
+    opts.fit = fit ? 1 : 0;
+    opts.inverse = inverse ? 1 : 0;
+    opts.min_alpha = min_alpha;
+    opts.expected = ptr<float>(o.expected);
+    auto ws = workspace(depth_map.device(), cugs_depth_loss_workspace_bytes(w, h), 9);
+    check(cugs_depth_loss(w, h, ptr<float>(d), ptr<float>(a), ptr<float>(t), &opts, ws.data_ptr(), ws.numel(),
+                          ptr<float>(out), ptr<float>(o.dL_ddepth_map), ptr<float>(o.dL_dalpha), stream_of(depth_map)),
+          "cugs_depth_loss");
+    o.loss = out[0]; o.scale_shift = out.slice(0, 1, 3); o.valid_weight = out[3]; o.valid_count = out[4]; o.fit_ok = out[5];
+    return o;
+}
+
 FusedAdam::FusedAdam(std::array<torch::Tensor, 5> params, std::array<float, 5> lrs, AdamHyper h)
     : params_(std::move(params)), lrs_(lrs), h_(h) {
     for (int i = 0; i < 5; ++i) { m_[i] = torch::zeros_like(params_[i]); v_[i] = torch::zeros_like(params_[i]); }

@@ -160,6 +160,20 @@ ExposureLoss combined_loss_exposure(const torch::Tensor& rendered, const torch::
                                     const torch::Tensor& exposure = {}, const torch::Tensor& mask = {},
                                     bool want_grad = true, bool want_corrected = false, int window_size = 11);
 
+// Not in the reference: depth supervision on render()'s depth and alpha maps.  The L1 loss of the
+// expected depth x = depth_map / alpha (`inverse`: alpha / depth_map, against an inverse-depth prior) against
+// s * target + b, all maps float32 [H,W] on one device; `weight` undefined: all ones.  A pixel counts iff alpha >
+// min_alpha, weight > 0, 0 < target < inf and (inverse) depth_map > 0; elsewhere the gradients and `expected` are 0; the
+// mean is over all H W pixels.  `align`: undefined for (1, 0), or a float32 [2] device tensor (s, b); `fit`: the weighted
+// least squares of the target to x, solved on the device in fp64 (fit_ok = 0 and (1, 0) when it is degenerate) - not
+// together with `align`.  (s, b) is a constant in the gradient.  Two launches (four with a fit), no host sync, the same
+// bits from run to run; the scalars are 0-dim device tensors, scale_shift a [2] view.  The gradients feed
+// render_backward's dL_ddepth_map and dL_dalpha.
+struct DepthLoss { torch::Tensor loss, dL_ddepth_map, dL_dalpha, scale_shift, valid_weight, valid_count, fit_ok, expected; };
+DepthLoss depth_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha, const torch::Tensor& target,
+                     const torch::Tensor& weight = {}, bool inverse = false, const torch::Tensor& align = {},
+                     bool fit = false, float min_alpha = 1e-3f, bool want_grad = true, bool want_expected = false);
+
 // optimizer/fused_adam.hpp:29-106 on raw tensors (group order: positions, sh, opacities, scales, rotations)
 struct AdamHyper { float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-15f; };
 class FusedAdam {

@@ -1,0 +1,71 @@
+// depth_loss_driver: the depth-supervision loss through the C++ host, for
+// tests/test_gpu_depth_loss_cpp.py.
+//   depth_loss_driver.bin <dir>
+// reads <dir>/manifest.txt:
+//   cases P            then P lines  "<h> <w> <inverse>"  -> case_<i>_d.f32, case_<i>_a.f32, case_<i>_t.f32 and
+//                                                            case_<i>_w.f32 (float32 [h,w]: depth map, alpha, target,
+//                                                            weight)
+// Writes, per case, out_<i>_out.f32 ({loss, s, b, valid weight, valid count, fit_ok}), out_<i>_gd.f32, out_<i>_ga.f32
+// and out_<i>_x.f32 ([h,w]: dL_ddepth_map, dL_dalpha, expected) from depth_loss with the weight and a fitted alignment.
+#include "cugs_hip_torch.hpp"
+
+#include <cstdio>
+#include <fstream>
+#include <string>
+#include <vector>
+
+static std::vector<float> read_f32(const std::string& path, size_t count) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
+    const std::streamsize bytes = f.tellg();
+    f.seekg(0);
+    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
+    f.read(reinterpret_cast<char*>(v.data()), bytes);
+    if (v.size() != count) { std::fprintf(stderr, "%s: %zu elements, expected %zu\n", path.c_str(), v.size(), count); std::exit(2); }
+    return v;
+}
+static void write_f32(const std::string& path, const torch::Tensor& t) {
+    auto host = t.contiguous().cpu();
+    std::ofstream f(path, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(host.data_ptr<float>()), host.numel() * sizeof(float));
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
+    const std::string dir = argv[1];
+    try {
+        const auto dev = torch::Device(torch::kCUDA, 0);
+        std::ifstream mf(dir + "/manifest.txt");
+        std::string word;
+        int ncases = 0;
+        if (!(mf >> word >> ncases) || word != "cases") { std::fprintf(stderr, "bad manifest\n"); return 2; }
+        auto load = [&](const std::string& name, int h, int w) {
+            auto v = read_f32(dir + "/" + name, static_cast<size_t>(h) * static_cast<size_t>(w));
+            return torch::from_blob(v.data(), {h, w}, torch::kFloat32).clone().to(dev);
+        };
+        for (int i = 0; i < ncases; ++i) {
+            int h = 0, w = 0, inverse = 0;
+            if (!(mf >> h >> w >> inverse)) { std::fprintf(stderr, "bad manifest line %d\n", i); return 2; }
+            const std::string stem = "case_" + std::to_string(i);
+            auto d = load(stem + "_d.f32", h, w), a = load(stem + "_a.f32", h, w), t = load(stem + "_t.f32", h, w);
+            auto wt = load(stem + "_w.f32", h, w);
+            const auto r = cugs_hip::depth_loss(d, a, t, wt, inverse != 0, {}, true, 1e-3f, true, true);
+            const std::string out = dir + "/out_" + std::to_string(i);
+            write_f32(out + "_out.f32", torch::cat({r.loss.reshape({1}), r.scale_shift, r.valid_weight.reshape({1}),
+                                                    r.valid_count.reshape({1}), r.fit_ok.reshape({1})}));
+            write_f32(out + "_gd.f32", r.dL_ddepth_map);
+            write_f32(out + "_ga.f32", r.dL_dalpha);
+            write_f32(out + "_x.f32", r.expected);
+        }
+        bool threw = false;                                       // a fit together with a given (s, b) is a c10::Error
+        if (ncases > 0) {
+            auto a = torch::ones({4, 4}, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
+            try { cugs_hip::depth_loss(a, a, a, {}, false, torch::ones({2}, a.options()), true); } catch (const c10::Error&) { threw = true; }
+        }
+        std::printf("depth_loss_driver ok cases=%d bad_args_throw=%d\n", ncases, threw ? 1 : 0);
+        return 0;
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "depth_loss_driver failed: %s\n", e.what());
+        return 4;
+    }
+}

@@ -2,7 +2,8 @@
 kernels (csrc/loss.hip): l1_loss, ssim, ssim_loss, combined_loss - plus combined_loss_and_grad, which
 returns the loss together with dL/dcolor, i.e. what trainer.cpp:214-217 obtains with clone + autograd + clone.
 combined_loss_exposure (not in the reference) is the same loss behind a per-view 3x4 exposure matrix
-and an optional pixel mask, both applied inside the same two kernels.
+and an optional pixel mask, both applied inside the same two kernels.  depth_loss (csrc/depth_loss.hip)
+is the depth-supervision loss on render()'s depth and alpha maps, with an optional scale/shift fit of the prior.
 Scalars come back as 0-dim device tensors (no host sync), as in the reference."""
 from __future__ import annotations
 
@@ -11,7 +12,7 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from ._lib import LossOpts, check, lib
+from ._lib import DepthLossOpts, LossOpts, check, lib
 from .rasterizer import _ptr, _stream, _torch_check, _workspace
 
 
@@ -117,3 +118,73 @@ def combined_loss_exposure(rendered: torch.Tensor, target: torch.Tensor, lambda_
     check(lib.cugs_combined_loss_opts(w, h, _ptr(r), _ptr(t), float(lambda_), int(window_size), C.byref(opts), _ptr(ws),
                                       ws.numel(), _ptr(out), None, _ptr(grad), _stream(dev)), "cugs_combined_loss_opts")
     return ExposureLoss(out[0], grad, d_exp, out[1], out[2], corrected)
+
+
+class DepthLoss(NamedTuple):
+    """depth_loss's results; the gradients and expected are None when not asked for."""
+    loss: torch.Tensor                       # 0-dim
+    dL_ddepth_map: Optional[torch.Tensor]    # [H,W]
+    dL_dalpha: Optional[torch.Tensor]        # [H,W]
+    scale_shift: torch.Tensor                # [2] = (s, b) the target was aligned with
+    valid_weight: torch.Tensor               # 0-dim: sum of the weights of the valid pixels
+    valid_count: torch.Tensor                # 0-dim float: number of valid pixels
+    fit_ok: torch.Tensor                     # 0-dim float: 0 when a fit was asked for and rejected, else 1
+    expected: Optional[torch.Tensor]         # [H,W] = x, 0 where invalid
+
+
+def _validate_map(t: torch.Tensor, name: str, h: int, w: int, dev: torch.device) -> None:
+    _torch_check(tuple(t.shape) == (h, w), f"{name} must be [H, W] = {(h, w)}, got {tuple(t.shape)}")
+    _torch_check(t.dtype == torch.float32, f"{name} must be float32, got {t.dtype}")
+    _torch_check(t.is_cuda and t.device == dev, f"{name} must be on the depth map's CUDA device")
+
+
+def depth_loss(depth_map: torch.Tensor, alpha: torch.Tensor, target: torch.Tensor,
+               weight: Optional[torch.Tensor] = None, inverse: bool = False, align=None, min_alpha: float = 1e-3,
+               want_grad: bool = True, want_expected: bool = False) -> DepthLoss:
+    """Depth supervision (not in the reference): the L1 loss of the expected depth x = depth_map / alpha
+    (inverse=True: x = alpha / depth_map, against an inverse-depth or disparity prior) against s * target + b, and its
+    gradients with respect to render()'s two maps:
+
+        d = depth_loss(out.depth_map, out.alpha, prior, align="fit")
+        render_backward(dL_dcolor, out, model, cam, settings, dL_ddepth_map=d.dL_ddepth_map, dL_dalpha=d.dL_dalpha)
+
+    All maps are float32 [H,W] on one CUDA device.  A pixel counts iff alpha > min_alpha, weight > 0 (None: all ones),
+    0 < target < inf (a NaN or 0 marks "no data") and, in inverse space, depth_map > 0; elsewhere both gradients and
+    `expected` are 0.  The mean is over all H*W pixels, so an invalid pixel counts as a perfect one.
+    align: None for (s, b) = (1, 0); a float32 [2] device tensor (s, b), e.g. precomputed per image; or "fit" for the
+    weighted least squares of the target to x over the valid pixels, solved on the device in fp64 - fit_ok is 0 and
+    (s, b) = (1, 0) when fewer than two pixels are valid or the target is constant.  (s, b) is a constant in the
+    gradient, as with a fit under no_grad.  Two launches (four with a fit), no host sync, no allocation beyond the
+    outputs, and the same bits from run to run.  Every scalar comes back as a 0-dim device tensor."""
+    _torch_check(depth_map.dim() == 2, f"depth_map must be 2-dimensional [H, W], got {depth_map.dim()} dims")
+    _torch_check(depth_map.dtype == torch.float32, f"depth_map must be float32, got {depth_map.dtype}")
+    _torch_check(depth_map.is_cuda, "depth_map must be on a CUDA device")
+    h, w = int(depth_map.shape[0]), int(depth_map.shape[1])
+    dev = depth_map.device
+    _validate_map(alpha, "alpha", h, w, dev)
+    _validate_map(target, "target", h, w, dev)
+    if weight is not None:
+        _validate_map(weight, "weight", h, w, dev)
+        weight = weight.contiguous()
+    _torch_check(0.0 < float(min_alpha) < float("inf"), f"min_alpha must be positive and finite, got {min_alpha}")
+    fit, given = False, None
+    if isinstance(align, str):
+        _torch_check(align == "fit", f'align must be None, "fit" or a float32 [2] tensor, got {align!r}')
+        fit = True
+    elif align is not None:
+        _torch_check(isinstance(align, torch.Tensor), f'align must be None, "fit" or a float32 [2] tensor, got {type(align).__name__}')
+        _torch_check(tuple(align.shape) == (2,), f"align must be [2] = (s, b), got {tuple(align.shape)}")
+        _torch_check(align.dtype == torch.float32, f"align must be float32, got {align.dtype}")
+        _torch_check(align.is_cuda and align.device == dev, "align must be on the depth map's CUDA device")
+        given = align.contiguous()
+    d, a, t = depth_map.contiguous(), alpha.contiguous(), target.contiguous()
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    g_d = torch.empty((h, w), dtype=torch.float32, device=dev) if want_grad else None
+    g_a = torch.empty((h, w), dtype=torch.float32, device=dev) if want_grad else None
+    expected = torch.empty((h, w), dtype=torch.float32, device=dev) if want_expected else None
+    opts = DepthLossOpts(weight=_ptr(weight), scale_shift=_ptr(given), fit=int(fit), inverse=int(bool(inverse)),
+                         min_alpha=float(min_alpha), expected=_ptr(expected))
+    ws = _workspace(dev, lib.cugs_depth_loss_workspace_bytes(w, h), "depth_loss")
+    check(lib.cugs_depth_loss(w, h, _ptr(d), _ptr(a), _ptr(t), C.byref(opts), _ptr(ws), ws.numel(), _ptr(out), _ptr(g_d),
+                              _ptr(g_a), _stream(dev)), "cugs_depth_loss")
+    return DepthLoss(out[0], g_d, g_a, out[1:3], out[3], out[4], out[5], expected)

@@ -493,6 +493,40 @@ int cugs_combined_loss_opts(int width, int height, const float* rendered, const 
                             int window_size, const cugs_loss_opts* opts, void* workspace, size_t workspace_bytes,
                             float* loss_out, float* ssim_map, float* dL_dcolor, void* stream);
 
+/* ---- Depth supervision: fused expected-depth L1 loss with a scale/shift fit (not in the reference) ----
+ * depth_map D, alpha A (cugs_blend_forward_opts::out_depth and the alpha of the blend), target t: DEVICE float[H*W].
+ * x = D / A in depth space, A / D in inverse space (against an inverse-depth or disparity target).  A pixel is VALID iff
+ * A > min_alpha, weight > 0, 0 < t < +inf (a NaN target is invalid) and, in inverse space, D > 0.
+ * The target is aligned as t' = s t + b (two roundings), (s, b) = (1, 0), `scale_shift`, or - fit - the weighted least
+ * squares min sum_valid w (s t + b - x)^2, solved on the device in fp64 from the sums w, w t, w x, w t^2, w t x (terms
+ * formed in double); accepted with >= 2 valid pixels and Sw Stt - St^2 > 1e-12 Sw Stt, else (1, 0) and fit_ok = 0.
+ * (s, b) is a CONSTANT in the gradient (a fit under no_grad): no term for ds/dx or db/dx.
+ *   r = x - t',  gx = (w sgn(r)) * (1.0f / (float)(H W)),  loss = (float)(sum_valid (double)(w |r|) / (H W)):
+ *   the mean is over ALL pixels whatever the mask - an invalid pixel counts as a perfect one.
+ *   depth space:   dL/dD = gx / A,          dL/dA = -((gx x) / A)
+ *   inverse space: dL/dD = -((gx x) / D),   dL/dA = gx / D
+ * At an invalid pixel both gradients and `expected` are 0; nothing there is NaN or inf.
+ * loss_out: DEVICE float[8] = {loss, s, b, sum of valid w, valid count, fit_ok, 0, 0} (the count is a float, exact
+ * below 2^24 pixels; fit_ok is 1 when nothing was fitted).  dL_ddepth_map and dL_dalpha ([H*W]) may each be NULL.
+ * Two launches without a fit, four with one; fp64 partials per workgroup reduced in a fixed order: the same bits from
+ * run to run, no float atomics, no host sync, no allocation.  16-byte accesses where every map is 16-byte aligned.
+ * All checks before anything is queued, in this order: CUGS_EINVAL for a non-positive size, a NULL depth_map, alpha,
+ * target, opts, workspace or loss_out, a min_alpha that is not positive and finite, fit together with scale_shift;
+ * CUGS_EWORKSPACE for a workspace shorter than cugs_depth_loss_workspace_bytes (0 for a negative size, a multiple of
+ * 256); CUGS_EOVERFLOW for H W > 2^31 - 1. */
+typedef struct cugs_depth_loss_opts {
+    const float* weight;       /* DEVICE float[H*W]; NULL: all ones */
+    const float* scale_shift;  /* DEVICE float[2] = (s, b); NULL: (1, 0) unless fit */
+    int          fit;          /* 1: fit (s, b) on the device; CUGS_EINVAL together with scale_shift */
+    int          inverse;      /* 0: D/A against depth; 1: A/D against inverse depth */
+    float        min_alpha;    /* > 0 and finite, else CUGS_EINVAL */
+    float*       expected;     /* optional DEVICE float[H*W]: x, 0 where invalid */
+} cugs_depth_loss_opts;
+size_t cugs_depth_loss_workspace_bytes(int width, int height);
+int cugs_depth_loss(int width, int height, const float* depth_map, const float* alpha, const float* target,
+                    const cugs_depth_loss_opts* opts, void* workspace, size_t workspace_bytes,
+                    float* loss_out /* DEVICE float[8] */, float* dL_ddepth_map, float* dL_dalpha, void* stream);
+
 /* ---- Evaluation metrics of one view (training/metrics.cpp:21-46: compute_psnr, compute_ssim) ---------------
  * rendered: [H,W,3] float.  The target is EITHER target_f32 ([H,W,3] float) OR target_u8 ([H,W,3] uint8, a cached
  * view at the camera's size, expanded in registers as (float)b * (1.0f / 255.0f): the bits of cugs_image_to_float
