@@ -136,7 +136,9 @@ __device__ __forceinline__ ActiveRect active_rect(unsigned long long active, flo
 // Hit groups.  Both blend kernels take the set bits of a sub-batch's hit mask FOUR at a time: the bits are popped first -
 // scalar work on the wave-uniform ballot - and the four per-pixel steps that follow are straight-line code with ONE
 // "is any pixel of mine still open" vote behind them instead of one per step.  A step taken after the last pixel closed
-// changes nothing: `open == 0` is folded into alpha, so the step's alpha, weight and gates are exactly 0.
+// changes nothing.  Forward: `open == 0` is folded into alpha, so the step's alpha and weight are exactly 0.  Backward:
+// a closed pixel has rem < 0, so k = sat(passf * rem) == 0 and with it al, weight and the gates are exactly 0; only
+// rem itself moves, further below zero.
 // The backward keeps the four LDS record indices (float4 units, < 768) in the 16-bit fields of one 64-bit scalar.
 // ---------------------------------------------------------------------------------------
 #define CUGS_HIT_GROUP 4
@@ -172,6 +174,13 @@ __device__ __forceinline__ unsigned long long cugs_set_hit(unsigned long long hi
 // four SIMDs, and the ~45 scalar instructions per step this produced cost more issue time than the
 // ~110 vector ones.)  The pixel's "still open" state is a float flag (1 or 0) multiplied into the
 // opacity, and skips become alpha = 0, which makes every later product exactly zero.
+// The two blends keep that state differently:
+//   * forward (and the score kernel): open = [T >= 1/255], recomputed from T in one instruction per step.  T never
+//     increases and a closed pixel has alpha = 0, so its T - and the flag - no longer change; a pixel outside the
+//     image starts with T = 0.  `open` IS folded into the opacity there: count, T and C must freeze.
+//   * backward: the counter rem = n_contrib - passers so far (an integer-valued float; closed <=> rem < 0) is the
+//     whole state.  It passes open = 1.0f here: a closed pixel that still sees a passer only takes rem further below
+//     zero (lists are far shorter than 2^24, so this stays exact) and the step's k = sat(passf * rem_before) is 0.
 //
 // Decisions are the oracle's, bit for bit.  FMA placement contract:
 //   u = fma(a,dx,b*dy); v = fma(b,dx,c*dy); q = fma(dx,u,dy*v); power = -0.5f*q (never formed here);
@@ -181,7 +190,7 @@ __device__ __forceinline__ unsigned long long cugs_set_hit(unsigned long long hi
 //     the minimum with 0.99, so alpha comes out negative and fails the 1/255 test;
 //   * power < -6: e = exp(-6)(1 + 1e-6) = 0.00248 and opacity <= 1, so alpha < 1/255 = 0.00392 is certain - the
 //     oracle reaches the same skip through its alpha test;
-//   * open == 0 -> alpha = 0 < 1/255 -> skipped.
+//   * open == 0 (forward, score kernel) -> alpha = 0 < 1/255 -> skipped.
 // Returns alpha if the Gaussian passes at this pixel, else exactly 0.
 struct PixelEval { float dx, dy, gx, gy, e; };
 // min(0.99, o e^power) with the power > 0 skip and the open flag folded in, BEFORE the alpha >= 1/255 test.
@@ -220,6 +229,8 @@ __device__ __forceinline__ float sat_fma(float a, float b, float c) {
     return __builtin_amdgcn_fmed3f(fmaf(a, b, c), 0.0f, 1.0f);
 }
 __device__ __forceinline__ float sat_add(float a, float b) { return __builtin_amdgcn_fmed3f(a + b, 0.0f, 1.0f); }
+// saturate(a*b) in one instruction (v_mul_f32 ... clamp).  NaN -> 0 (dx10 clamp).
+__device__ __forceinline__ float sat_mul(float a, float b) { return __builtin_amdgcn_fmed3f(a * b, 0.0f, 1.0f); }
 
 // 1.0f if x >= 1/255 (the reference's `alpha < 1/255 -> skip`, forward.cu:141 / backward.cu:137) else 0.0f, exactly,
 // for every non-NaN x <= 2^31: with p = the float just below 1/255, x >= 1/255 <=> x > p <=> x - p >= ulp = 2^-31.

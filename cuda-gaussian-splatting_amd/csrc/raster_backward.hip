@@ -18,7 +18,11 @@
 // The kernel is bound by VALU issue (profiles/README.md), so the step is written for instruction
 // count, priced with the measured costs in cugs_raster_common.h:
 //   * every per-lane decision is a 0/1 float made by `v_fma ... clamp` and multiplied in: no v_cmp /
-//     v_cndmask pairs.  The Q1 counter is `rem` = n_contrib - passers so far, `open` = sat(rem + 1);
+//     v_cndmask pairs.  The Q1 counter `rem` = n_contrib - passers so far is the pixel's whole state: it is open
+//     while rem >= 0, and a step contributes where k = sat(passf * rem_before) - ONE v_mul ... clamp.  The open flag
+//     is not folded into the opacity here (the forward needs that, to freeze count, T and C): a closed pixel that
+//     still sees a passer only takes rem further below zero, k stays 0, and with k == 0 the step's al, weight and
+//     gates are exactly 0 and rcp(1) = 1 - T and D keep their bits;
 //   * the colour accumulators S_c (backward.cu:83-87, 196-198) only ever enter as sum_c dL/dC_c S_c:
 //     that ONE dot product D is carried instead (D += weight * G, G = sum_c dL/dC_c c_c);
 //   * the five geometric gradients are accumulated as the MOMENTS of dL/dpower over the pixel offsets,
@@ -157,15 +161,16 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
     if (DEPTH && inside && dL_dalpha) D = fmaf(-T, dL_dalpha[pix], D);    // the alpha map: channel (c = 0, bg = -1)
     // rem = n_contrib - (passing Gaussians seen so far, counted from the END: Q1).  A pixel stops - without
     // contributing - at the passer that takes rem below zero (backward.cu:141-145); a pixel with
-    // n_contrib == 0, or outside the image, starts out finished.  open == sat(rem + 1) throughout.
+    // n_contrib == 0, or outside the image, starts out finished.  A pixel is open <=> rem >= 0; rem is an
+    // integer-valued float, and a finished pixel that sees further passers only takes it further below zero (exact: a
+    // tile list is far shorter than 2^24).
     float rem = (inside && max_contrib > 0) ? (float)max_contrib : -1.0f;
-    float open = (inside && max_contrib > 0) ? 1.0f : 0.0f;
-    bool wave_done = (__ballot(open != 0.0f) == 0ull);
+    bool wave_done = (__ballot(rem >= 0.0f) == 0ull);
     // The hit loop works in GROUPS of CUGS_BWD_HITS hits: the record indices are popped from the sub-batch's hit mask
     // first (scalar work, constant shifts), then the four phase-1 steps run as straight-line code with constant
     // contribution slots, ONE "all my pixels are closed" vote follows, then phase 2.  `pending` counts the hits of an
     // unfinished group: popped into hitrecs[0 .. pending) at the end of a sub-batch, NOT yet evaluated; the next
-    // sub-batch of the same 256-record batch tops the group up (its cull then sees an `open` that is up to three steps
+    // sub-batch of the same 256-record batch tops the group up (its cull then sees open pixels up to three steps
     // old - a larger rectangle, so still conservative), the end of the batch runs what is left one step at a time.
     int pending = 0;                                            // wave-uniform, 0 .. CUGS_BWD_HITS - 1 between groups
     unsigned st_steps = 0, st_contrib = 0, st_lanes = 0, st_batches = 0, st_tested = 0, st_open = 0;   // STATS only
@@ -247,11 +252,13 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
 
         // ---- decisions (backward.cu:123-145) as 0/1 floats
         PixelEval e;
-        const float alpha = pixel_alpha_raw(pxf, pyf, g0.x, g0.y, g0.z, g0.w, g1.x, o, open, e);
-        const float passf = passes_alpha_min(alpha);           // alpha >= 1/255 (0 for a finished pixel)
+        // open = 1.0f: the counter alone closes a pixel (see the header comment); o * 1.0f folds away
+        const float alpha = pixel_alpha_raw(pxf, pyf, g0.x, g0.y, g0.z, g0.w, g1.x, o, 1.0f, e);
+        const float passf = passes_alpha_min(alpha);           // alpha >= 1/255: exactly 0 or 1
+        // 1: this Gaussian contributes here - it passes and rem >= 1 BEFORE it is counted (the passer that takes rem
+        // below zero stops the pixel without contributing, Q1); rem <= 0, a finished pixel included, clamps to 0
+        const float k = sat_mul(passf, rem);
         rem -= passf;                                          // contributors counted from the END (Q1)
-        open = sat_add(rem, 1.0f);                             // 0 once a passer fell beyond n_contrib
-        const float k = passf * open;                          // 1: this Gaussian contributes here
         const float al = alpha * k;
         // clamp gate (backward.cu:181-191): o e >= 0.99 <=> alpha == 0.99f zeroes dL/do and dL/dpower,
         // dL/drgb still flows
@@ -267,7 +274,7 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
         D = fmaf(weight, G, D);
         if (STATS) {
             const unsigned long long lm = __ballot(k != 0.0f);
-            if (lm) { ++st_contrib; st_lanes += __popcll(lm); st_open += __popcll(__ballot(open != 0.0f)); }
+            if (lm) { ++st_contrib; st_lanes += __popcll(lm); st_open += __popcll(__ballot(rem >= 0.0f)); }
         }
         s_contrib[wave][slot][lane] = make_float2(weight, gate * e.e);
     };
@@ -289,7 +296,7 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
             const int nsub = (batch_count + CUGS_WAVE - 1) / CUGS_WAVE;
             for (int sub = nsub - 1; sub >= 0 && !wave_done; --sub) {
                 const int j = sub * CUGS_WAVE + lane;
-                const ActiveRect ar = active_rect(__ballot(open != 0.0f), qx0, qy0);   // !wave_done => non-empty
+                const ActiveRect ar = active_rect(__ballot(rem >= 0.0f), qx0, qy0);   // !wave_done => non-empty
                 bool hit = false;
                 if (j < batch_count)
                     hit = may_touch_quad(s_rec[j * CUGS_REC_F4 + 0], s_rec[j * CUGS_REC_F4 + 1], ar.x0, ar.y0, ar.wx,
@@ -310,9 +317,10 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
                     step(cugs_hit(hitrecs, 1), 1);
                     step(cugs_hit(hitrecs, 2), 2);
                     step(cugs_hit(hitrecs, 3), 3);
-                    // ONE vote per group.  A step taken after the last pixel closed has k == 0 in every lane: al = 0,
-                    // rcp(1) = 1, weight = gate = 0 - T, D and rem stay, the sums gain +0.0f.
-                    const bool closed = (__ballot(open != 0.0f) == 0ull);
+                    // ONE vote per group.  A step taken after the last pixel closed has rem < 0, so k == 0, in every
+                    // lane: al = 0, rcp(1) = 1, weight = gate = 0 - T and D stay, rem only sinks further, the sums gain
+                    // a zero.
+                    const bool closed = (__ballot(rem >= 0.0f) == 0ull);
                     flush(CUGS_BWD_HITS);
                     if (closed) { wave_done = true; mask = 0ull; break; }
                 }
@@ -324,7 +332,7 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
             }
             if (pending) {                 // the partial group: before s_rec is re-staged (and at the end of the wave's walk)
                 for (int p = 0; p < pending; ++p) step(cugs_hit(hitrecs, p), p);
-                if (__ballot(open != 0.0f) == 0ull) wave_done = true;
+                if (__ballot(rem >= 0.0f) == 0ull) wave_done = true;
                 flush(pending);
                 pending = 0;
             }

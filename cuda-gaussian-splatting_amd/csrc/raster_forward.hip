@@ -61,7 +61,9 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
     const int num_batches = (num_in_range + CUGS_BLOCK - 1) / CUGS_BLOCK;
 
     typedef float v2f __attribute__((ext_vector_type(2)));
-    float T = 1.0f, C0 = 0.0f;
+    // T of a pixel outside the image starts at 0: open = [T >= 1/255] is then 0 for it from the first step on, its
+    // weight al * T is 0, and nothing of it is stored
+    float T = inside ? 1.0f : 0.0f, C0 = 0.0f;
     v2f C12 = {0.0f, 0.0f};                             // green/blue as one packed-fp32 accumulator (v_pk_fma_f32)
     v2f C0Z = {0.0f, 0.0f};                             // DEPTH: red and depth likewise (record words 8, 9)
     float count = 0.0f;                                 // contributors: a float counter (exact below 2^24 per tile list)
@@ -84,8 +86,9 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
         C12 = __builtin_elementwise_fma((v2f){weight, weight}, (v2f){col.z, col.w}, C12);   // record words 10,11: an aligned pair
         T *= (1.0f - al);
         count += passf;
-        open *= passes_alpha_min(T);                            // T < 1/255 -> done (forward.cu:150-156): the same
-                                                                // threshold; only a passing Gaussian can lower T
+        // T < 1/255 -> done (forward.cu:150-156): the same threshold.  T never increases, and a closed pixel has
+        // al == 0, so its T - and this flag - no longer change: no product with the old flag is needed
+        open = passes_alpha_min(T);
     };
 
     for (int batch = 0; batch < num_batches; ++batch) {

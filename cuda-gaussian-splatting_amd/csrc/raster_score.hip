@@ -114,7 +114,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_blend_scores(RasterGeom geo, Ras
     const int num_in_range = range_end - range_start;
     const int num_batches = (num_in_range + CUGS_BLOCK - 1) / CUGS_BLOCK;
 
-    float T = 1.0f;
+    float T = inside ? 1.0f : 0.0f;                     // outside the image: closed from the start, as in the forward
     float open = inside ? 1.0f : 0.0f;                  // 1 while the pixel still blends, 0 once T < 1/255
     bool wave_done = (__ballot(open != 0.0f) == 0ull);
     const int row = lane >> 4;                          // reduce4_sum_max: row r delivers step {0, 2, 1, 3}[r]
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_blend_scores(RasterGeom geo, Ras
         const float al = alpha * passf;
         weight = al * T;                                        // the forward's product: exactly 0 where skipped or closed
         T *= (1.0f - al);
-        open *= passes_alpha_min(T);
+        open = passes_alpha_min(T);                             // the forward's flag chain: T never increases
         passed = (unsigned)__popcll(__ballot(passf != 0.0f));
         g = __float_as_int(g1.w);
     };
