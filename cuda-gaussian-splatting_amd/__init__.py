@@ -20,6 +20,8 @@ from .fused_adam import (AdamConfig, FusedAdam, ParamGroup, PositionLRConfig,  #
 from .loss import (DepthLoss, ExposureLoss, combined_loss, combined_loss_and_grad, combined_loss_exposure,  # noqa: F401
                    depth_loss, l1_loss, ssim, ssim_loss)
 from .exposure import ExposureModel  # noqa: F401
+from .bilagrid import (BilagridGrad, BilateralGridModel, bilagrid_slice, bilagrid_slice_backward,  # noqa: F401
+                       bilagrid_tv)
 from .densification import DensificationConfig, DensificationController, DensificationStats  # noqa: F401
 from .mcmc import MCMCConfig, MCMCController, MCMCStats  # noqa: F401
 from .gaussian_init import init_gaussians_from_sparse, knn_mean_distances  # noqa: F401

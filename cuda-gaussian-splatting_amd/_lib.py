@@ -85,6 +85,11 @@ class DepthLossOpts(C.Structure):
     _fields_ = [("weight", C.c_void_p), ("scale_shift", C.c_void_p), ("fit", C.c_int), ("inverse", C.c_int),
                 ("min_alpha", C.c_float), ("expected", C.c_void_p)]
 
+
+class BilagridDims(C.Structure):
+    """struct cugs_bilagrid_dims."""
+    _fields_ = [("l", C.c_int32), ("gy", C.c_int32), ("gx", C.c_int32)]
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -145,6 +150,10 @@ SIGNATURES = {
     "cugs_combined_loss_opts": (_I, [_I, _I, _P, _P, _F, _I, C.POINTER(LossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_depth_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_depth_loss": (_I, [_I, _I, _P, _P, _P, C.POINTER(DepthLossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
+    "cugs_bilagrid_workspace_bytes": (C.c_size_t, [_I, _I, C.POINTER(BilagridDims)]),
+    "cugs_bilagrid_slice": (_I, [_I, _I, C.POINTER(BilagridDims), _P, _P, _P, _P]),
+    "cugs_bilagrid_slice_backward": (_I, [_I, _I, C.POINTER(BilagridDims), _P, _P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "cugs_bilagrid_tv": (_I, [C.POINTER(BilagridDims), _P, _F, _P, _P, _I, _P]),
     "cugs_eval_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_eval_metrics": (_I, [_I, _I, _P, _P, _P, _I, _P, C.c_size_t, _P, _P]),
     "cugs_densify_accumulate": (_I, [_L, _P, _P, _P, _P, _P, _P]),

@@ -761,6 +761,77 @@ DepthLoss depth_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha,
     return o;
 }
 
+namespace {
+void validate_image(const torch::Tensor& img, const char* name) {
+    TORCH_CHECK(img.dim() == 3 && img.size(2) == 3, name, " must be [H, W, 3], got ", img.sizes());
+    TORCH_CHECK(img.dtype() == torch::kFloat32, name, " must be float32, got ", img.dtype());
+    TORCH_CHECK(img.is_cuda(), name, " must be on a CUDA device");
+}
+cugs_bilagrid_dims validate_grid(const torch::Tensor& grid, const torch::Device* dev) {
+    TORCH_CHECK(grid.dim() == 4 && grid.size(0) == 12, "grid must be [12, L, GY, GX], got ", grid.sizes());
+    for (int a = 1; a < 4; ++a)
+        TORCH_CHECK(grid.size(a) >= 2 && grid.size(a) <= 64, "grid extents L, GY, GX must lie in [2, 64], got ", grid.sizes());
+    TORCH_CHECK(grid.dtype() == torch::kFloat32, "grid must be float32, got ", grid.dtype());
+    TORCH_CHECK(grid.is_cuda() && (!dev || grid.device() == *dev), "grid must be on the image's CUDA device");
+    TORCH_CHECK(grid.is_contiguous(), "grid must be contiguous");
+    cugs_bilagrid_dims d;
+    d.l = static_cast<int32_t>(grid.size(1)); d.gy = static_cast<int32_t>(grid.size(2)); d.gx = static_cast<int32_t>(grid.size(3));
+    return d;
+}
+}  // namespace
+
+torch::Tensor bilagrid_slice(const torch::Tensor& grid, const torch::Tensor& rendered) {
+    validate_image(rendered, "rendered");
+    const auto dev = rendered.device();
+    const auto dims = validate_grid(grid, &dev);
+    auto r = rendered.contiguous();
+    auto out = torch::empty_like(r);
+    check(cugs_bilagrid_slice(static_cast<int>(r.size(1)), static_cast<int>(r.size(0)), &dims, ptr<float>(grid), ptr<float>(r),
+                              ptr<float>(out), stream_of(r)), "cugs_bilagrid_slice");
+    return out;
+}
+
+BilagridGrad bilagrid_slice_backward(const torch::Tensor& grid, const torch::Tensor& rendered,
+                                     const torch::Tensor& dL_dcorrected, bool want_grid_grad, bool want_image_grad) {
+    validate_image(rendered, "rendered");
+    validate_image(dL_dcorrected, "dL_dcorrected");
+    TORCH_CHECK(dL_dcorrected.sizes() == rendered.sizes(), "dL_dcorrected must have rendered's shape ", rendered.sizes(),
+                ", got ", dL_dcorrected.sizes());
+    TORCH_CHECK(dL_dcorrected.device() == rendered.device(), "dL_dcorrected must be on rendered's CUDA device");
+    const auto dev = rendered.device();
+    const auto dims = validate_grid(grid, &dev);
+    const int h = static_cast<int>(rendered.size(0)), w = static_cast<int>(rendered.size(1));
+    auto r = rendered.contiguous(), g = dL_dcorrected.contiguous();
+    BilagridGrad o;
+    if (want_image_grad) o.dL_drendered = torch::empty_like(r);
+    if (want_grid_grad) o.dL_dgrid = torch::empty_like(grid);
+    torch::Tensor ws;
+    if (want_grid_grad) ws = workspace(dev, cugs_bilagrid_workspace_bytes(w, h, &dims), 10);
+    check(cugs_bilagrid_slice_backward(w, h, &dims, ptr<float>(grid), ptr<float>(r), ptr<float>(g),
+                                       ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? static_cast<size_t>(ws.numel()) : 0,
+                                       ptr<float>(o.dL_drendered), ptr<float>(o.dL_dgrid), stream_of(r)),
+          "cugs_bilagrid_slice_backward");
+    return o;
+}
+
+BilagridTV bilagrid_tv(const torch::Tensor& grid, float weight, const torch::Tensor& dL_dgrid) {
+    const auto dims = validate_grid(grid, nullptr);
+    BilagridTV o;
+    const bool accumulate = dL_dgrid.defined();
+    if (accumulate) {
+        TORCH_CHECK(dL_dgrid.sizes() == grid.sizes() && dL_dgrid.dtype() == torch::kFloat32 && dL_dgrid.device() == grid.device() &&
+                    dL_dgrid.is_contiguous(), "dL_dgrid must be a contiguous float32 tensor of the grid's shape and device");
+        o.dL_dgrid = dL_dgrid;
+    } else {
+        o.dL_dgrid = torch::empty_like(grid);
+    }
+    auto tv = torch::empty({1}, fopt(grid));
+    check(cugs_bilagrid_tv(&dims, ptr<float>(grid), weight, ptr<float>(tv), ptr<float>(o.dL_dgrid), accumulate ? 1 : 0,
+                           stream_of(grid)), "cugs_bilagrid_tv");
+    o.tv = tv[0];
+    return o;
+}
+
 FusedAdam::FusedAdam(std::array<torch::Tensor, 5> params, std::array<float, 5> lrs, AdamHyper h)
     : params_(std::move(params)), lrs_(lrs), h_(h) {
     for (int i = 0; i < 5; ++i) { m_[i] = torch::zeros_like(params_[i]); v_[i] = torch::zeros_like(params_[i]); }

@@ -174,6 +174,24 @@ DepthLoss depth_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha,
                      const torch::Tensor& weight = {}, bool inverse = false, const torch::Tensor& align = {},
                      bool fit = false, float min_alpha = 1e-3f, bool want_grad = true, bool want_expected = false);
 
+// Not in the reference: per-view bilateral-grid colour correction.  grid: float32 [12, L, GY, GX],
+// contiguous, each extent in [2, 64], coefficient 4 i + j = row i, column j of [A | b]; images float32 [H,W,3] on the
+// grid's device.  bilagrid_slice: corrected = A(p) rendered(p) + b(p), the transform sampled trilinearly at
+// (x / (W-1), y / (H-1), luma) - grid_sample(bilinear, align_corners, border) + the affine apply in one launch; the
+// identity grid returns rendered bit for bit.  bilagrid_slice_backward: dL_drendered (with the gradient through the
+// luminance guidance) and dL_dgrid (written, not accumulated; fixed-order sums, no float atomics, the same bits from
+// run to run), each only when asked for.  bilagrid_tv: tv = the UNWEIGHTED total variation (0-dim), dL_dgrid = weight *
+// dtv/dgrid, ADDED to the tensor given (bilagrid_slice_backward's) or written to a new one.  No host sync anywhere.
+// The loop: render -> bilagrid_slice -> combined_loss_and_grad(corrected, target) -> bilagrid_slice_backward ->
+// render_backward(dL_drendered); held-out views are evaluated without a grid.
+struct BilagridGrad { torch::Tensor dL_drendered, dL_dgrid; };
+struct BilagridTV { torch::Tensor tv, dL_dgrid; };
+torch::Tensor bilagrid_slice(const torch::Tensor& grid, const torch::Tensor& rendered);
+BilagridGrad bilagrid_slice_backward(const torch::Tensor& grid, const torch::Tensor& rendered,
+                                     const torch::Tensor& dL_dcorrected, bool want_grid_grad = true,
+                                     bool want_image_grad = true);
+BilagridTV bilagrid_tv(const torch::Tensor& grid, float weight = 1.0f, const torch::Tensor& dL_dgrid = {});
+
 // optimizer/fused_adam.hpp:29-106 on raw tensors (group order: positions, sh, opacities, scales, rotations)
 struct AdamHyper { float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-15f; };
 class FusedAdam {

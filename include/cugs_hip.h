@@ -527,6 +527,50 @@ int cugs_depth_loss(int width, int height, const float* depth_map, const float* 
                     const cugs_depth_loss_opts* opts, void* workspace, size_t workspace_bytes,
                     float* loss_out /* DEVICE float[8] */, float* dL_ddepth_map, float* dL_dalpha, void* stream);
 
+/* ---- Bilateral-grid colour correction: fused slice, backward and TV loss (not in the reference) ----
+ * grid G: DEVICE float[12, L, GY, GX], coefficient k = 4 i + j = row i, column j of a 3x4 transform [A | b]; the identity
+ * grid holds [I | 0] at every vertex; 2 <= L, GY, GX <= 64.  rendered c, corrected, dL_dcorrected g, dL_drendered:
+ * DEVICE float[H, W, 3].  The fp32 operation order (every step one correctly rounded operation), for pixel (x, y):
+ *   sx = (float)(GX-1) / (float)(W-1), 0 when W = 1 (sy likewise; formed once on the host)
+ *   fx = (float)x * sx;  x0 = min((int)fx, GX-2);  tx = fx - (float)x0            (y likewise)
+ *   luma = (0.299f r + 0.587f g) + 0.114f b;  zs = luma * (float)(L-1);  fz = min(max(zs, 0), (float)(L-1))
+ *   z0 = min((int)fz, L-2);  tz = fz - (float)z0;  inside = 0 <= zs <= L-1
+ *   lerp(a, b, t) = a + t * (b - a); per coefficient k, a.. = G[k] at level z0, b.. at z0+1 (rows y0, y0+1; columns x0, x0+1):
+ *     p0 = lerp(lerp(a00, a01, tx), lerp(a10, a11, tx), ty);  p1 likewise from b..;  D_k = p1 - p0;  E_k = p0 + tz * D_k
+ *   corrected_i = ((E[4i] r + E[4i+1] g) + E[4i+2] b) + E[4i+3]
+ * i.e. trilinear weights wx wy wz, w = t or 1 - t, on the eight corners: grid_sample(bilinear, align_corners, border) at
+ * (x / (W-1), y / (H-1), luma) followed by the affine apply.  Backward:
+ *   q_i = ((D[4i] r + D[4i+1] g) + D[4i+2] b) + D[4i+3];  s = inside ? ((g_0 q_0 + g_1 q_1) + g_2 q_2) * (float)(L-1) : 0
+ *   dL_drendered_j = ((E[j] g_0 + E[4+j] g_1) + E[8+j] g_2) + s * lw_j,  lw = (0.299f, 0.587f, 0.114f)
+ *   dL_dgrid[k, z, y, x] = sum_p w(p; z, y, x) g_i(p) [c(p), 1]_j,  w = {1-ty, ty} {1-tx, tx} {1-tz at z0, tz at z0+1}
+ * The term s lw is the gradient through the luminance guidance; it is 0 where the clamp is active.  The lerp form makes a
+ * lattice that is constant over a pixel's corners exact, so the identity grid returns rendered, and dL_drendered = g, bit
+ * for bit (a -0.0 input comes back +0.0).  dL_dgrid is WRITTEN, not accumulated: per-workgroup fp32 partials over the
+ * xy-cells of the lattice (a fixed tree), combined per element in fp64 in a fixed order - no float atomics, no host sync,
+ * no allocation, the same bits from run to run.  Either of dL_drendered, dL_dgrid may be NULL (both: nothing is queued).
+ * cugs_bilagrid_workspace_bytes = round256(4 * 48 * L * (GX-1)(GY-1) * Q), Q = ceil(pixels of the largest xy-cell / 1024)
+ * (the [cell][chunk][z][corner][12] partials; 0 for a bad size or lattice); needed only with dL_dgrid.
+ * cugs_bilagrid_tv: tv = sum over the axes z, y, x of mean((G[.., i+1, ..] - G[.., i, ..])^2), each mean over the
+ * 12 (n_axis - 1) (other two extents) differences of that axis; differences, squares and sums in fp64; tv_out (DEVICE
+ * float[1]) gets the UNWEIGHTED tv, dL_dgrid gets weight * dtv/dG (accumulate != 0: that is added to what it holds, one
+ * fp32 add per element - so it can follow cugs_bilagrid_slice_backward on the same buffer).  One launch, one workgroup.
+ * Either output may be NULL, not both.
+ * All checks before anything is queued, in this order.  slice / slice_backward: CUGS_EINVAL for a non-positive size, NULL
+ * dims, an extent outside [2, 64], a NULL grid, rendered, corrected / dL_dcorrected, dL_dgrid without workspace;
+ * CUGS_EWORKSPACE for dL_dgrid with a short workspace; CUGS_EOVERFLOW for H W > 2^31 - 1.  tv: CUGS_EINVAL for NULL dims,
+ * an extent outside [2, 64], a NULL grid, or both outputs NULL. */
+typedef struct cugs_bilagrid_dims {
+    int32_t l, gy, gx;      /* vertices along luminance, y, x: each in [2, 64] */
+} cugs_bilagrid_dims;
+size_t cugs_bilagrid_workspace_bytes(int width, int height, const cugs_bilagrid_dims* dims);
+int cugs_bilagrid_slice(int width, int height, const cugs_bilagrid_dims* dims, const float* grid, const float* rendered,
+                        float* corrected, void* stream);
+int cugs_bilagrid_slice_backward(int width, int height, const cugs_bilagrid_dims* dims, const float* grid,
+                                 const float* rendered, const float* dL_dcorrected, void* workspace,
+                                 size_t workspace_bytes, float* dL_drendered, float* dL_dgrid, void* stream);
+int cugs_bilagrid_tv(const cugs_bilagrid_dims* dims, const float* grid, float weight, float* tv_out /* DEVICE float[1] */,
+                     float* dL_dgrid, int accumulate, void* stream);
+
 /* ---- Evaluation metrics of one view (training/metrics.cpp:21-46: compute_psnr, compute_ssim) ---------------
  * rendered: [H,W,3] float.  The target is EITHER target_f32 ([H,W,3] float) OR target_u8 ([H,W,3] uint8, a cached
  * view at the camera's size, expanded in registers as (float)b * (1.0f / 255.0f): the bits of cugs_image_to_float
