@@ -1,6 +1,7 @@
 // sort_bin.h — direct binning: the pair level as one counting sort by tile id.
 #pragma once
 
+#include "sort_bin_cover.h"
 #include "sort_tile_order.h"
 
 namespace {
@@ -179,10 +180,13 @@ __global__ __launch_bounds__(BIN_NT) void k_bin_scan(uint32_t rows, uint32_t til
 }
 
 // A WAVE per (group of the depth order, block of 8 x 8 tiles): lane = tile, the next free slot of the lane's tile lives in a
-// register, and the wave walks - in depth order - the records of the group whose rectangle touches its block; each one
-// is ONE masked store: the lanes inside the rectangle write the Gaussian's index to their tile's slot and advance.
-// Stable by construction (one wave per tile, records in order): no atomics, no ranking, no LDS round trip in the loop, and
-// tens of thousands of independent waves that hide each other's latencies.
+// register, and the wave walks - in depth order - the records of the group whose rectangle touches its block.  STAGE: each
+// one is ONE masked step, the lanes inside the rectangle take the Gaussian's index for their tile's slot and advance
+// (~25 dependent, mostly scalar instructions per hit).  Direct: the hits are gathered 64 at a time, lane = hit forms the
+// cover mask of the block, a bit-matrix transpose across the wave turns that into lane = tile, and every tile lane pops
+// its own hits in order (bin_pop_batch below; 80 -> 64 us at 1 M Gaussians / 8.4 M pairs).
+// Stable by construction (one wave per tile, records in order): no atomics, no ranking, and tens of thousands of
+// independent waves that hide each other's latencies.
 // A workgroup is up to eight horizontally adjacent blocks.  Its waves first share out a pre-filter - each takes a slice of the
 // group's records straight from memory and lists in LDS, in order, the ones that touch the workgroup's 8-row, <= 64-column
 // window (one in twelve at 1080p), with their Gaussian index - and every wave then tests only the listed ones against its
@@ -199,6 +203,90 @@ constexpr int BIN_RUN = 16;                       // entries a lane collects bef
                                                   // on the dense 1080p view; 8: three per CU, 0.277-0.285; without the buffer 0.345)
 constexpr int BIN_RUN_STRIDE = BIN_RUN + 3;       // LDS row stride in dwords: odd (the lanes' rows start in different banks), and the
                                                   // flush reads up to three entries beyond `held`
+// ---- the direct (not STAGE) variant's walk: lanes = hits -> lanes = tiles through a bit-matrix transpose ----
+// Orders this wave's LDS traffic for the compiler: what the lanes wrote before is what any lane reads after.  (The LDS
+// itself executes one wave's instructions in order; no instruction comes out of this.)
+__device__ __forceinline__ void bin_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+template <int CTRL>
+__device__ __forceinline__ uint32_t bin_dpp(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+// One block-swap stage of the transpose inside a dword: v = this lane's row, p = the row of lane ^ S, M = the bit
+// positions with (position & S) == 0.  The lane without bit S keeps those and takes the partner's from them, moved up
+// by S; the lane with bit S keeps the others and takes the partner's from them, moved down.  Both are a rotation of p
+// (no bit that is taken wraps) and one v_bfi with the lane's keep mask: no branch, whatever the lane.
+template <int S, uint32_t M>
+__device__ __forceinline__ uint32_t bin_tr_merge(uint32_t v, uint32_t p, bool upper) {
+    const uint32_t keep = upper ? ~M : M;
+    const uint32_t moved = __builtin_rotateright32(p, upper ? (uint32_t)S : 32u - (uint32_t)S);
+    return (v & keep) | (moved & ~keep);
+}
+// 64 x 64 bit-matrix transpose across the wave: in, lane c holds row c (bit t of {hi, lo}); out, lane t holds column t
+// (bit c).  Six block-swap stages on the two dwords: 32 is one v_permlane32_swap (lo of the upper half <-> hi of the
+// lower half, exactly the two off-diagonal 32 x 32 blocks), 16 goes through ds_bpermute (a v_permlane16_swap wants a
+// copy and a select per dword), 8 / 4 / 2 / 1 are DPP: row_ror:8, row_half_mirror then quad_perm [3,2,1,0] (= lane ^ 4),
+// quad_perm [2,3,0,1], quad_perm [1,0,3,2].  All 64 lanes must be active.
+__device__ __forceinline__ void bin_transpose64(uint32_t& lo, uint32_t& hi, uint32_t lane) {
+    {
+        const auto r = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
+        lo = r[0]; hi = r[1];
+    }
+    {
+        const bool up = (lane & 16u) != 0u;
+        const uint32_t pl = (uint32_t)__shfl_xor((int)lo, 16), ph = (uint32_t)__shfl_xor((int)hi, 16);
+        lo = bin_tr_merge<16, 0x0000FFFFu>(lo, pl, up); hi = bin_tr_merge<16, 0x0000FFFFu>(hi, ph, up);
+    }
+    {
+        const bool up = (lane & 8u) != 0u;
+        const uint32_t pl = bin_dpp<0x128>(lo), ph = bin_dpp<0x128>(hi);
+        lo = bin_tr_merge<8, 0x00FF00FFu>(lo, pl, up); hi = bin_tr_merge<8, 0x00FF00FFu>(hi, ph, up);
+    }
+    {
+        const bool up = (lane & 4u) != 0u;
+        const uint32_t pl = bin_dpp<0x1B>(bin_dpp<0x141>(lo)), ph = bin_dpp<0x1B>(bin_dpp<0x141>(hi));
+        lo = bin_tr_merge<4, 0x0F0F0F0Fu>(lo, pl, up); hi = bin_tr_merge<4, 0x0F0F0F0Fu>(hi, ph, up);
+    }
+    {
+        const bool up = (lane & 2u) != 0u;
+        const uint32_t pl = bin_dpp<0x4E>(lo), ph = bin_dpp<0x4E>(hi);
+        lo = bin_tr_merge<2, 0x33333333u>(lo, pl, up); hi = bin_tr_merge<2, 0x33333333u>(hi, ph, up);
+    }
+    {
+        const bool up = (lane & 1u) != 0u;
+        const uint32_t pl = bin_dpp<0xB1>(lo), ph = bin_dpp<0xB1>(hi);
+        lo = bin_tr_merge<1, 0x55555555u>(lo, pl, up); hi = bin_tr_merge<1, 0x55555555u>(hi, ph, up);
+    }
+}
+// Writes one batch of buffered hits (hits[0 .. count), count <= 64, in depth order; wave-uniform call, all lanes active).
+// Lane c forms hit c's cover of the block; after the transpose lane t holds the hits that cover ITS tile and pops them in
+// ascending order = depth order: the hit's Gaussian index from LDS to the tile's next slot.  A per-lane loop under EXEC,
+// as long as the fullest tile of the batch; nothing per hit on the scalar unit.
+__device__ __forceinline__ void bin_pop_batch(const uint2* hits, uint32_t count, uint32_t lane, uint32_t blk_tx0,
+                                              uint32_t blk_ty0, bool tile_ok, char* outb, uint32_t& pos) {
+    bin_wave_lds_sync();
+    const uint64_t cover = lane < count ? bin_cover_mask(hits[lane].x, blk_tx0, blk_ty0) : 0ull;
+    uint32_t lo = (uint32_t)cover, hi = (uint32_t)(cover >> 32);
+    bin_transpose64(lo, hi, lane);
+    if (!tile_ok) lo = hi = 0u;                                       // a tile outside the image never stores
+    const uint32_t* const word = reinterpret_cast<const uint32_t*>(hits);     // hit b's Gaussian: word 2 b + 1
+    while (lo != 0u) {
+        const uint32_t b = (uint32_t)__builtin_ctz(lo);
+        lo &= lo - 1u;
+        *reinterpret_cast<uint32_t*>(outb + pos) = word[2u * b + 1u];
+        pos += 4u;
+    }
+    while (hi != 0u) {
+        const uint32_t b = (uint32_t)__builtin_ctz(hi);
+        hi &= hi - 1u;
+        *reinterpret_cast<uint32_t*>(outb + pos) = word[2u * b + 65u];
+        pos += 4u;
+    }
+    bin_wave_lds_sync();                                              // the buffer is free again
+}
+
 template <bool STAGE>
 __global__ __launch_bounds__(BIN_WG_WAVES * CUGS_WAVE) void k_bin_scatter(
     uint32_t n, uint32_t group, uint32_t nbx, uint32_t nby, uint32_t gxs, uint32_t pairs_or_cap, bool predicted,
@@ -209,6 +297,7 @@ __global__ __launch_bounds__(BIN_WG_WAVES * CUGS_WAVE) void k_bin_scatter(
     int32_t* __restrict__ tile_ranges, uint32_t* __restrict__ tile_order, const uint32_t* __restrict__ win) {
     __shared__ uint2 s_cand[BIN_WG_WAVES][BIN_SLICE];                 // {packed rectangle, Gaussian} of the listed records
     __shared__ uint32_t s_cnt[BIN_WG_WAVES];
+    __shared__ uint2 s_hit[STAGE ? 1 : BIN_WG_WAVES * CUGS_WAVE];     // direct: a wave's batch of hits, {packed rectangle, Gaussian}
     __shared__ uint32_t s_run[STAGE ? BIN_WG_WAVES * CUGS_WAVE * BIN_RUN_STRIDE + 4 : 1];   // (+ the read-ahead of the last row's flush)
     const uint32_t nt = blockDim.x, nw = nt >> 6, tid = threadIdx.x, wid = tid >> 6, lane = tid & 63u;
     const uint32_t per_group = nby * gxs;
@@ -318,6 +407,8 @@ __global__ __launch_bounds__(BIN_WG_WAVES * CUGS_WAVE) void k_bin_scatter(
     char* const outb = reinterpret_cast<char*>(out);
     uint32_t* const run = s_run + (STAGE ? tid * BIN_RUN_STRIDE : 0u);      // STAGE: this lane's collected indices
     uint32_t held = 0u;
+    uint2* const hits = s_hit + (STAGE ? 0u : wid * CUGS_WAVE);       // direct: this wave's batch and how many hits it holds
+    uint32_t nhit = 0u;
     const uint32_t base = blk * group;
     const uint32_t end = min(n, base + group);                        // base < end: the grid covers ceil(n / group) groups
     const uint32_t stage = nw * BIN_SLICE;
@@ -350,6 +441,30 @@ __global__ __launch_bounds__(BIN_WG_WAVES * CUGS_WAVE) void k_bin_scatter(
         }
         __syncthreads();
         if (!active) continue;
+        if constexpr (!STAGE) {
+            // The lists one after the other, 64 candidates at a time: the lanes whose candidate touches the block append
+            // it to the wave's batch at the ballot prefix (depth order kept), and every 64 hits the batch is written by
+            // bin_pop_batch.  What is left rides on to the next list, the next stage, and is written after the group.
+            const uint32_t cnts = s_cnt[lane & (uint32_t)(BIN_WG_WAVES - 1)];      // all the lists' lengths in one read
+            for (uint32_t w2 = 0; w2 < nw; ++w2) {
+                const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cnts, (int)w2);
+                for (uint32_t k0 = 0; k0 < c; k0 += CUGS_WAVE) {
+                    const uint2 rec = s_cand[w2][k0 + lane];          // (k0 + lane < BIN_SLICE; beyond c: stale, not a hit)
+                    const uint32_t x0v = rec.x & 127u, wv = (rec.x >> 14) & 127u;
+                    const bool hit = k0 + lane < c && (int32_t)rec.x >= 0 && x0v < blk_x1 && x0v + wv > blk_x0;
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+                    const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, nhit));
+                    if (hit && slot < (uint32_t)CUGS_WAVE) hits[slot] = rec;
+                    nhit = (uint32_t)__builtin_amdgcn_readfirstlane((int)(nhit + (uint32_t)__popcll(m)));   // (in an SGPR)
+                    if (nhit >= (uint32_t)CUGS_WAVE) {                // (wave-uniform)
+                        bin_pop_batch(hits, (uint32_t)CUGS_WAVE, lane, blk_x0, win_y0, tile_ok, outb, pos);
+                        if (hit && slot >= (uint32_t)CUGS_WAVE) hits[slot - (uint32_t)CUGS_WAVE] = rec;
+                        nhit -= (uint32_t)CUGS_WAVE;
+                    }
+                }
+            }
+            continue;
+        }
         for (uint32_t w2 = 0; w2 < nw; ++w2) {                        // the slices' lists one after the other: depth order
             const uint32_t c = s_cnt[w2];
             for (uint32_t k0 = 0; k0 < c; k0 += CUGS_WAVE) {
@@ -390,6 +505,9 @@ __global__ __launch_bounds__(BIN_WG_WAVES * CUGS_WAVE) void k_bin_scatter(
                 }
             }
         }
+    }
+    if constexpr (!STAGE) {
+        if (nhit != 0u) bin_pop_batch(hits, nhit, lane, blk_x0, win_y0, tile_ok, outb, pos);      // the rest of the group
     }
     if constexpr (STAGE) {                                            // what the lanes still hold
         for (uint32_t q = 0; __ballot(q < held) != 0ull; ++q)
