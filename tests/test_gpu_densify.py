@@ -106,6 +106,7 @@ def test_moments_ride_along_and_edges(pkg, do, dev):
         opt.m_[i] = torch.randn_like(opt.m_[i])
         opt.v_[i] = torch.rand_like(opt.v_[i])
     m_before = [t.clone() for t in opt.m_]
+    v_before = [t.clone() for t in opt.v_]
     g = torch.Generator().manual_seed(1)
     ctrl.accumulate_gradients((torch.randn((n, 2), generator=g) * 0.0005).to(dev), torch.ones(n, dtype=torch.int32, device=dev))
     flags, _ = ctrl._classify(ours, 5)
@@ -116,6 +117,7 @@ def test_moments_ride_along_and_edges(pkg, do, dev):
     for i in range(5):
         assert opt.m_[i].shape == getattr(ours, opt._names[i]).shape == opt.v_[i].shape
         assert torch.equal(opt.m_[i][:kept], m_before[i][keep])                  # survivors keep their moments
+        assert torch.equal(opt.v_[i][:kept], v_before[i][keep])
         assert float(opt.m_[i][kept:].abs().sum()) == 0.0 and float(opt.v_[i][kept:].abs().sum()) == 0.0
     # everything pruned -> an empty, still valid model
     ctrl = pkg.DensificationController(pkg.DensificationConfig(densify_from=0, densify_every=5, opacity_threshold=0.999999,
