@@ -17,8 +17,8 @@ from .rasterizer import (evaluate_sh_backward_cuda, evaluate_sh_cuda, project_ba
                          sh_backward_views, sort_gaussians)
 from .fused_adam import (AdamConfig, FusedAdam, ParamGroup, PositionLRConfig,  # noqa: F401
                          active_sh_degree_for_step, lr_defaults, position_lr)
-from .loss import (DepthLoss, ExposureLoss, combined_loss, combined_loss_and_grad, combined_loss_exposure,  # noqa: F401
-                   depth_loss, l1_loss, ssim, ssim_loss)
+from .loss import (DepthLoss, ExposureLoss, NormalLoss, combined_loss, combined_loss_and_grad,  # noqa: F401
+                   combined_loss_exposure, depth_loss, depth_to_normals, l1_loss, normal_loss, ssim, ssim_loss)
 from .exposure import ExposureModel  # noqa: F401
 from .bilagrid import (BilagridGrad, BilateralGridModel, bilagrid_slice, bilagrid_slice_backward,  # noqa: F401
                        bilagrid_tv)

@@ -86,6 +86,12 @@ class DepthLossOpts(C.Structure):
                 ("min_alpha", C.c_float), ("expected", C.c_void_p)]
 
 
+class NormalLossOpts(C.Structure):
+    """struct cugs_normal_loss_opts."""
+    _fields_ = [("weight", C.c_void_p), ("normals_out", C.c_void_p), ("cos_weight", C.c_float), ("l1_weight", C.c_float),
+                ("min_alpha", C.c_float)]
+
+
 class BilagridDims(C.Structure):
     """struct cugs_bilagrid_dims."""
     _fields_ = [("l", C.c_int32), ("gy", C.c_int32), ("gx", C.c_int32)]
@@ -150,6 +156,8 @@ SIGNATURES = {
     "cugs_combined_loss_opts": (_I, [_I, _I, _P, _P, _F, _I, C.POINTER(LossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_depth_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_depth_loss": (_I, [_I, _I, _P, _P, _P, C.POINTER(DepthLossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
+    "cugs_normal_loss_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "cugs_normal_loss": (_I, [_I, _I, _F, _F, _F, _F, _P, _P, _P, C.POINTER(NormalLossOpts), _P, C.c_size_t, _P, _P, _P, _P]),
     "cugs_bilagrid_workspace_bytes": (C.c_size_t, [_I, _I, C.POINTER(BilagridDims)]),
     "cugs_bilagrid_slice": (_I, [_I, _I, C.POINTER(BilagridDims), _P, _P, _P, _P]),
     "cugs_bilagrid_slice_backward": (_I, [_I, _I, C.POINTER(BilagridDims), _P, _P, _P, _P, C.c_size_t, _P, _P, _P]),

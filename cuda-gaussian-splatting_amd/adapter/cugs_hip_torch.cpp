@@ -761,6 +761,61 @@ DepthLoss depth_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha,
     return o;
 }
 
+NormalLoss normal_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha, float fx, float fy, float cx, float cy,
+                       const torch::Tensor& target, const torch::Tensor& weight, float cos_weight, float l1_weight,
+                       float min_alpha, bool want_grad, bool want_normals) {
+    TORCH_CHECK(depth_map.dim() == 2, "depth_map must be 2-dimensional [H, W], got ", depth_map.dim(), " dims");
+    TORCH_CHECK(depth_map.dtype() == torch::kFloat32, "depth_map must be float32, got ", depth_map.dtype());
+    TORCH_CHECK(depth_map.is_cuda(), "depth_map must be on a CUDA device");
+    const int h = static_cast<int>(depth_map.size(0)), w = static_cast<int>(depth_map.size(1));
+    auto validate_map = [&](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.dim() == 2 && t.size(0) == h && t.size(1) == w, name, " must be [H, W], got ", t.sizes());
+        TORCH_CHECK(t.dtype() == torch::kFloat32, name, " must be float32, got ", t.dtype());
+        TORCH_CHECK(t.is_cuda() && t.device() == depth_map.device(), name, " must be on the depth map's CUDA device");
+    };
+    validate_map(alpha, "alpha");
+    TORCH_CHECK(fx > 0.0f && std::isfinite(fx) && fy > 0.0f && std::isfinite(fy), "fx, fy must be positive and finite, got ", fx, ", ", fy);
+    TORCH_CHECK(std::isfinite(cx) && std::isfinite(cy), "cx, cy must be finite, got ", cx, ", ", cy);
+    TORCH_CHECK(min_alpha > 0.0f && std::isfinite(min_alpha), "min_alpha must be positive and finite, got ", min_alpha);
+    TORCH_CHECK(cos_weight >= 0.0f && std::isfinite(cos_weight) && l1_weight >= 0.0f && std::isfinite(l1_weight),
+                "cos_weight and l1_weight must be non-negative and finite, got ", cos_weight, ", ", l1_weight);
+    torch::Tensor t, wt;
+    if (target.defined()) {
+        TORCH_CHECK(target.dim() == 3 && target.size(0) == 3 && target.size(1) == h && target.size(2) == w,
+                    "target must be [3, H, W], got ", target.sizes());
+        TORCH_CHECK(target.dtype() == torch::kFloat32, "target must be float32, got ", target.dtype());
+        TORCH_CHECK(target.is_cuda() && target.device() == depth_map.device(), "target must be on the depth map's CUDA device");
+        TORCH_CHECK(cos_weight > 0.0f || l1_weight > 0.0f, "cos_weight and l1_weight must not both be 0");
+        t = target.contiguous();
+    } else {
+        TORCH_CHECK(!weight.defined(), "weight needs a target");
+        TORCH_CHECK(want_normals, "without a target there is only the normal map: want_normals must be set");
+    }
+    if (weight.defined()) { validate_map(weight, "weight"); wt = weight.contiguous(); }
+    auto d = depth_map.contiguous(), a = alpha.contiguous();
+    auto out = torch::empty({8}, fopt(depth_map));
+    NormalLoss o;
+    if (want_grad && t.defined()) { o.dL_ddepth_map = torch::empty({h, w}, fopt(depth_map)); o.dL_dalpha = torch::empty({h, w}, fopt(depth_map)); }
+    if (want_normals) o.normals = torch::empty({3, h, w}, fopt(depth_map));
+    cugs_normal_loss_opts opts{};
+    opts.weight = ptr<float>(wt);
+    opts.normals_out = ptr<float>(o.normals);
+    opts.cos_weight = cos_weight;
+    opts.l1_weight = l1_weight;
+    opts.min_alpha = min_alpha;
+    auto ws = workspace(depth_map.device(), cugs_normal_loss_workspace_bytes(w, h), 11);
+    check(cugs_normal_loss(w, h, fx, fy, cx, cy, ptr<float>(d), ptr<float>(a), ptr<float>(t), &opts, ws.data_ptr(), ws.numel(),
+                           ptr<float>(out), ptr<float>(o.dL_ddepth_map), ptr<float>(o.dL_dalpha), stream_of(depth_map)),
+          "cugs_normal_loss");
+    o.loss = out[0]; o.valid_weight = out[1]; o.valid_count = out[2];
+    return o;
+}
+
+torch::Tensor depth_to_normals(const torch::Tensor& depth_map, const torch::Tensor& alpha, float fx, float fy, float cx,
+                               float cy, float min_alpha) {
+    return normal_loss(depth_map, alpha, fx, fy, cx, cy, {}, {}, 1.0f, 0.0f, min_alpha, false, true).normals;
+}
+
 namespace {
 void validate_image(const torch::Tensor& img, const char* name) {
     TORCH_CHECK(img.dim() == 3 && img.size(2) == 3, name, " must be [H, W, 3], got ", img.sizes());

@@ -174,6 +174,22 @@ DepthLoss depth_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha,
                      const torch::Tensor& weight = {}, bool inverse = false, const torch::Tensor& align = {},
                      bool fit = false, float min_alpha = 1e-3f, bool want_grad = true, bool want_expected = false);
 
+// Not in the reference: normal supervision from render()'s depth and alpha maps.  The surface normal of
+// the expected depth depth_map / alpha (back-projected through the pinhole fx, fy, cx, cy; central differences; n = Py x
+// Px normalised - the 2DGS depth_to_normal, camera axes x right, y down, z forward, pointing at the camera) against a
+// normal prior `target` float32 [3,H,W] (normalised in the kernel): the mean over all H W pixels of weight *
+// (cos_weight (1 - n.t) + l1_weight |n - t|_1) over the pixels that count - not on the image border, alpha > min_alpha
+// there and at the four neighbours, a normal and a prior vector of finite non-zero length, weight > 0 (`weight`
+// undefined: all ones).  The masks are constants in the gradient; the gradients feed render_backward's dL_ddepth_map and
+// dL_dalpha.  `target` undefined: the normal map alone (want_normals must be set; loss 0, no gradients).  Two launches, no
+// host sync, the same bits from run to run and whatever the tiling; the scalars are 0-dim device tensors.
+struct NormalLoss { torch::Tensor loss, dL_ddepth_map, dL_dalpha, valid_weight, valid_count, normals; };
+NormalLoss normal_loss(const torch::Tensor& depth_map, const torch::Tensor& alpha, float fx, float fy, float cx, float cy,
+                       const torch::Tensor& target = {}, const torch::Tensor& weight = {}, float cos_weight = 1.0f,
+                       float l1_weight = 0.0f, float min_alpha = 1e-3f, bool want_grad = true, bool want_normals = false);
+torch::Tensor depth_to_normals(const torch::Tensor& depth_map, const torch::Tensor& alpha, float fx, float fy, float cx,
+                               float cy, float min_alpha = 1e-3f);
+
 // Not in the reference: per-view bilateral-grid colour correction.  grid: float32 [12, L, GY, GX],
 // contiguous, each extent in [2, 64], coefficient 4 i + j = row i, column j of [A | b]; images float32 [H,W,3] on the
 // grid's device.  bilagrid_slice: corrected = A(p) rendered(p) + b(p), the transform sampled trilinearly at

@@ -25,6 +25,7 @@
 // Every float step below is one correctly rounded operation (-ffp-contract=off, IEEE division); tests/depth_loss_ref.py
 // is its numpy mirror, op for op.
 #include "cugs_common.h"
+#include "cugs_row_sums.h"   // block_sums, reduce_rows
 
 #include <math.h>
 
@@ -80,26 +81,6 @@ __device__ __forceinline__ bool expected_depth(float D, float A, float t, float 
     return valid;
 }
 
-// N fp64 sums of the workgroup -> row[0..N): over the wave by shuffles, then the four waves in order.
-template <int N>
-__device__ __forceinline__ void block_sums(double (&acc)[N], double* __restrict__ row) {
-    __shared__ double s_red[N][CUGS_BLOCK / CUGS_WAVE];
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        for (int d = CUGS_WAVE / 2; d >= 1; d >>= 1) acc[k] += __shfl_xor(acc[k], d);
-    if ((tid & (CUGS_WAVE - 1)) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s_red[k][tid / CUGS_WAVE] = acc[k];
-    }
-    __syncthreads();
-    if (tid < N) {
-        double a = s_red[tid][0];
-        for (int v = 1; v < CUGS_BLOCK / CUGS_WAVE; ++v) a += s_red[tid][v];
-        row[tid] = a;
-    }
-}
-
 template <bool INV, bool HAS_W>
 __global__ __launch_bounds__(CUGS_BLOCK) void k_depth_stats(int64_t n, const float* __restrict__ D,
                                                             const float* __restrict__ A, const float* __restrict__ t,
@@ -119,29 +100,6 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_depth_stats(int64_t n, const flo
         }
     }
     block_sums<NFIT>(acc, partials + (size_t)NFIT * blockIdx.x);
-}
-
-// Rows of N fp64 partials -> s_acc[k][0], the order of loss.hip's finalize_loss: thread t takes rows t, t + 256, ...;
-// then a tree.  Call with the whole workgroup.
-template <int N>
-__device__ __forceinline__ void reduce_rows(const double* __restrict__ partials, int nblk, double (*s_acc)[CUGS_BLOCK]) {
-    double a[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) a[k] = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += CUGS_BLOCK) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) a[k] += partials[(size_t)N * i + k];
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) s_acc[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int d = CUGS_BLOCK / 2; d >= 1; d >>= 1) {
-        if ((int)threadIdx.x < d) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) s_acc[k][threadIdx.x] += s_acc[k][threadIdx.x + d];
-        }
-        __syncthreads();
-    }
 }
 
 // min sum w (s t + b - x)^2: the normal equations by Cramer's rule in fp64.  Accepted with two or more valid pixels

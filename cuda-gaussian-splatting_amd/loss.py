@@ -3,7 +3,8 @@ kernels (csrc/loss.hip): l1_loss, ssim, ssim_loss, combined_loss - plus combined
 returns the loss together with dL/dcolor, i.e. what trainer.cpp:214-217 obtains with clone + autograd + clone.
 combined_loss_exposure (not in the reference) is the same loss behind a per-view 3x4 exposure matrix
 and an optional pixel mask, both applied inside the same two kernels.  depth_loss (csrc/depth_loss.hip)
-is the depth-supervision loss on render()'s depth and alpha maps, with an optional scale/shift fit of the prior.
+is the depth-supervision loss on render()'s depth and alpha maps, with an optional scale/shift fit of the prior;
+normal_loss and depth_to_normals (csrc/normal_loss.hip) are the normal supervision on the same two maps.
 Scalars come back as 0-dim device tensors (no host sync), as in the reference."""
 from __future__ import annotations
 
@@ -12,8 +13,9 @@ from typing import NamedTuple, Optional, Tuple
 
 import torch
 
-from ._lib import DepthLossOpts, LossOpts, check, lib
+from ._lib import DepthLossOpts, LossOpts, NormalLossOpts, check, lib
 from .rasterizer import _ptr, _stream, _torch_check, _workspace
+from .types import CameraInfo
 
 
 def _validate(img: torch.Tensor, name: str) -> None:
@@ -188,3 +190,79 @@ def depth_loss(depth_map: torch.Tensor, alpha: torch.Tensor, target: torch.Tenso
     check(lib.cugs_depth_loss(w, h, _ptr(d), _ptr(a), _ptr(t), C.byref(opts), _ptr(ws), ws.numel(), _ptr(out), _ptr(g_d),
                               _ptr(g_a), _stream(dev)), "cugs_depth_loss")
     return DepthLoss(out[0], g_d, g_a, out[1:3], out[3], out[4], out[5], expected)
+
+
+class NormalLoss(NamedTuple):
+    """normal_loss's results; the gradients and normals are None when not asked for (or, the gradients, without a prior)."""
+    loss: torch.Tensor                       # 0-dim
+    dL_ddepth_map: Optional[torch.Tensor]    # [H,W]
+    dL_dalpha: Optional[torch.Tensor]        # [H,W]
+    valid_weight: torch.Tensor               # 0-dim: sum of the weights of the loss-valid pixels
+    valid_count: torch.Tensor                # 0-dim float: number of loss-valid pixels
+    normals: Optional[torch.Tensor]          # [3,H,W] = n^, 0 where not normal-valid
+
+
+def normal_loss(depth_map: torch.Tensor, alpha: torch.Tensor, camera: CameraInfo, target: Optional[torch.Tensor] = None,
+                weight: Optional[torch.Tensor] = None, cos_weight: float = 1.0, l1_weight: float = 0.0,
+                min_alpha: float = 1e-3, want_grad: bool = True, want_normals: bool = False) -> NormalLoss:
+    """Normal supervision from the rendered depth (not in the reference): the surface normal of the
+    expected depth depth_map / alpha - back-projected through the camera's pinhole intrinsics, central differences,
+    n = Py x Px normalised: the 2DGS depth_to_normal, in camera axes (x right, y down, z forward) and pointing at the
+    camera - against a normal prior `target` [3,H,W] in the same axes, and the gradients to render()'s two maps:
+
+        n = normal_loss(out.depth_map, out.alpha, cam, prior)
+        render_backward(dL_dcolor, out, model, cam, settings, dL_ddepth_map=n.dL_ddepth_map, dL_dalpha=n.dL_dalpha)
+
+    loss = mean over all H*W pixels of weight * (cos_weight * (1 - n.t) + l1_weight * |n - t|_1) on the pixels that
+    count: not on the image border, alpha > min_alpha there and at the four neighbours, a normal of finite non-zero
+    length, weight > 0 (None: all ones) and a prior vector of finite non-zero length (a zero or NaN vector marks "no
+    data"; the prior is normalised in the kernel).  The masks are constants in the gradient; both gradients are 0 where
+    a pixel takes part in no counted stencil.  target=None only computes the normal map (loss 0, no gradients).  Two
+    launches, no host sync, no allocation beyond the outputs, the same bits from run to run and whatever the tiling.
+    Every scalar comes back as a 0-dim device tensor."""
+    _torch_check(depth_map.dim() == 2, f"depth_map must be 2-dimensional [H, W], got {depth_map.dim()} dims")
+    _torch_check(depth_map.dtype == torch.float32, f"depth_map must be float32, got {depth_map.dtype}")
+    _torch_check(depth_map.is_cuda, "depth_map must be on a CUDA device")
+    h, w = int(depth_map.shape[0]), int(depth_map.shape[1])
+    dev = depth_map.device
+    _validate_map(alpha, "alpha", h, w, dev)
+    _torch_check(isinstance(camera, CameraInfo), f"camera must be a CameraInfo, got {type(camera).__name__}")
+    K = camera.intrinsics
+    fx, fy, cx, cy = float(K.fx), float(K.fy), float(K.cx), float(K.cy)
+    inf = float("inf")
+    _torch_check(0.0 < fx < inf and 0.0 < fy < inf, f"camera fx, fy must be positive and finite, got {fx}, {fy}")
+    _torch_check(-inf < cx < inf and -inf < cy < inf, f"camera cx, cy must be finite, got {cx}, {cy}")
+    _torch_check(0.0 < float(min_alpha) < inf, f"min_alpha must be positive and finite, got {min_alpha}")
+    _torch_check(0.0 <= float(cos_weight) < inf and 0.0 <= float(l1_weight) < inf,
+                 f"cos_weight and l1_weight must be non-negative and finite, got {cos_weight}, {l1_weight}")
+    if target is not None:
+        _torch_check(tuple(target.shape) == (3, h, w), f"target must be [3, H, W] = {(3, h, w)}, got {tuple(target.shape)}")
+        _torch_check(target.dtype == torch.float32, f"target must be float32, got {target.dtype}")
+        _torch_check(target.is_cuda and target.device == dev, "target must be on the depth map's CUDA device")
+        _torch_check(float(cos_weight) > 0.0 or float(l1_weight) > 0.0, "cos_weight and l1_weight must not both be 0")
+        target = target.contiguous()
+    else:
+        _torch_check(weight is None, "weight needs a target")
+        _torch_check(want_normals, "without a target there is only the normal map: want_normals must be True")
+    if weight is not None:
+        _validate_map(weight, "weight", h, w, dev)
+        weight = weight.contiguous()
+    d, a = depth_map.contiguous(), alpha.contiguous()
+    want_grad = bool(want_grad) and target is not None
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    g_d = torch.empty((h, w), dtype=torch.float32, device=dev) if want_grad else None
+    g_a = torch.empty((h, w), dtype=torch.float32, device=dev) if want_grad else None
+    normals = torch.empty((3, h, w), dtype=torch.float32, device=dev) if want_normals else None
+    opts = NormalLossOpts(weight=_ptr(weight), normals_out=_ptr(normals), cos_weight=float(cos_weight),
+                          l1_weight=float(l1_weight), min_alpha=float(min_alpha))
+    ws = _workspace(dev, lib.cugs_normal_loss_workspace_bytes(w, h), "normal_loss")
+    check(lib.cugs_normal_loss(w, h, fx, fy, cx, cy, _ptr(d), _ptr(a), _ptr(target), C.byref(opts), _ptr(ws), ws.numel(),
+                               _ptr(out), _ptr(g_d), _ptr(g_a), _stream(dev)), "cugs_normal_loss")
+    return NormalLoss(out[0], g_d, g_a, out[1], out[2], normals)
+
+
+def depth_to_normals(depth_map: torch.Tensor, alpha: torch.Tensor, camera: CameraInfo,
+                     min_alpha: float = 1e-3) -> torch.Tensor:
+    """The normal map [3,H,W] of normal_loss without a prior: what one looks at to judge the geometry (0 on the image
+    border and wherever alpha <= min_alpha at the pixel or one of its four neighbours)."""
+    return normal_loss(depth_map, alpha, camera, None, min_alpha=min_alpha, want_normals=True).normals

@@ -527,6 +527,46 @@ int cugs_depth_loss(int width, int height, const float* depth_map, const float* 
                     const cugs_depth_loss_opts* opts, void* workspace, size_t workspace_bytes,
                     float* loss_out /* DEVICE float[8] */, float* dL_ddepth_map, float* dL_dalpha, void* stream);
 
+/* ---- Normal supervision from the rendered depth: fused depth-to-normal loss (not in the reference) ----
+ * depth_map D, alpha A: DEVICE float[H*W] as above; target t: DEVICE float[3*H*W] (planes x, y, z: a normal prior in
+ * camera axes x right, y down, z forward, of any length), or NULL for the normal map alone.  Pinhole fx, fy, cx, cy;
+ * pixel centres at u + 0.5, v + 0.5.  The fp32 operation order (every step one correctly rounded operation):
+ *   depth-valid: A > min_alpha;  d = D / A there, 0 elsewhere
+ *   ax(u) = (((float)u + 0.5f) - cx) / fx,  ay(v) likewise;  P = (ax d, ay d, d)
+ *   Px = P(u+1, v) - P(u-1, v),  Py = P(u, v+1) - P(u, v-1),  n = Py x Px (towards the camera: n_z < 0 on a visible
+ *   surface, the 2DGS depth_to_normal),  nn = (n_x^2 + n_y^2) + n_z^2,  rl = 1.0f / sqrtf(nn),  n^ = n rl
+ *   normal-valid: not on the image border, the pixel and its four neighbours depth-valid, 0 < nn < inf; n^ = 0 elsewhere
+ *   tt = (t_x^2 + t_y^2) + t_z^2,  t^ = t (1.0f / sqrtf(tt))
+ *   loss-valid: normal-valid, weight > 0, 0 < tt < inf (a zero or non-finite prior vector marks "no data")
+ *   l = w (cos_weight (1 - ((n^_x t^_x + n^_y t^_y) + n^_z t^_z)) + l1_weight ((|e_x| + |e_y|) + |e_z|)),  e = n^ - t^
+ *   loss = (float)(sum_loss-valid (double)l / (H W)): the mean is over ALL pixels, as in cugs_depth_loss.
+ * Backward, the masks held constant:  b = (w (1.0f / (float)(H W))) (l1_weight sgn(e) - cos_weight t^),
+ *   c = (b - n^ ((n^_x b_x + n^_y b_y) + n^_z b_z)) rl,  gPx = c x Py,  gPy = Px x c  (0 where not loss-valid), then the
+ *   GATHER  gP(u,v) = ((gPx(u-1,v) - gPx(u+1,v)) + gPy(u,v-1)) - gPy(u,v+1),  g_d = (gP_x ax + gP_y ay) + gP_z,
+ *   dL/dD = g_d / A,  dL/dA = -((g_d d) / A);  both +0 where none of the four neighbours is loss-valid.
+ * loss_out: DEVICE float[8] = {loss, sum of loss-valid w, loss-valid count, 0, 0, 0, 0, 0}; all 0 without a target.
+ * dL_ddepth_map and dL_dalpha ([H*W]) may each be NULL.  Two launches (the fused forward + backward over 64x16 tiles, one
+ * workgroup of fixed-order fp64 sums); no atomics, no host sync, no allocation, the same bits from run to run, and a
+ * pixel's result does not depend on the tiling.  4-byte accesses only: no alignment beyond float's is asked for.
+ * All checks before anything is queued, in this order: CUGS_EINVAL for a non-positive size, a NULL depth_map, alpha,
+ * opts, workspace or loss_out, a min_alpha that is not positive and finite, fx or fy not positive and finite, cx or cy
+ * not finite, a loss weight that is negative or not finite, both loss weights 0 with a target, and without a target a
+ * NULL normals_out or a non-NULL weight, dL_ddepth_map or dL_dalpha; CUGS_EWORKSPACE for a workspace shorter than
+ * cugs_normal_loss_workspace_bytes (0 for a negative size, a multiple of 256: 24 bytes per tile); CUGS_EOVERFLOW for
+ * H W > 2^31 - 1. */
+typedef struct cugs_normal_loss_opts {
+    const float* weight;       /* DEVICE float[H*W]; NULL: all ones */
+    float*       normals_out;  /* optional DEVICE float[3*H*W]: n^, 0 where not normal-valid */
+    float        cos_weight;   /* >= 0 and finite */
+    float        l1_weight;    /* >= 0 and finite; not both 0 with a target */
+    float        min_alpha;    /* > 0 and finite, else CUGS_EINVAL */
+} cugs_normal_loss_opts;
+size_t cugs_normal_loss_workspace_bytes(int width, int height);
+int cugs_normal_loss(int width, int height, float fx, float fy, float cx, float cy, const float* depth_map,
+                     const float* alpha, const float* target /* nullable */, const cugs_normal_loss_opts* opts,
+                     void* workspace, size_t workspace_bytes, float* loss_out /* DEVICE float[8] */,
+                     float* dL_ddepth_map, float* dL_dalpha, void* stream);
+
 /* ---- Bilateral-grid colour correction: fused slice, backward and TV loss (not in the reference) ----
  * grid G: DEVICE float[12, L, GY, GX], coefficient k = 4 i + j = row i, column j of a 3x4 transform [A | b]; the identity
  * grid holds [I | 0] at every vertex; 2 <= L, GY, GX <= 64.  rendered c, corrected, dL_dcorrected g, dL_drendered:
