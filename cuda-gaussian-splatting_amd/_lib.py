@@ -62,6 +62,11 @@ class PoseGrad(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+class ProjectionOpts(C.Structure):
+    """struct cugs_projection_opts (C.pointer(block) for mcmc and pose: the field keeps the block alive)."""
+    _fields_ = [("mcmc", C.POINTER(McmcFused)), ("pose", C.POINTER(PoseGrad)), ("sparse", C.c_int)]
+
+
 class BlendForwardOpts(C.Structure):
     """struct cugs_blend_forward_opts."""
     _fields_ = [("zero_buf", C.c_void_p), ("zero_bytes", C.c_size_t), ("tile_order", C.c_void_p),
@@ -176,20 +181,11 @@ SIGNATURES = {
     "cugs_mcmc_relocate_workspace_bytes": (C.c_size_t, [_L]),
     "cugs_mcmc_relocate": (_I, [_L, _I, _P, _P, _P, _P, _P, _F, _F, _F, _U64, _U32, C.POINTER(_P), C.POINTER(_P), _P,
                                 C.c_size_t, _P, _P, _P]),
-    "cugs_project_backward_adam_mcmc": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
-                                             C.POINTER(AdamFused), C.POINTER(McmcFused), _P, _P]),
     "cugs_pose_grad_workspace_bytes": (C.c_size_t, [_L]),
-    "cugs_project_backward_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F,
-                                        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(PoseGrad), _P]),
-    "cugs_project_backward_adam_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
-                                             C.POINTER(AdamFused), _P, C.POINTER(PoseGrad), _P]),
-    "cugs_project_backward_adam_mcmc_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
-                                                  C.POINTER(AdamFused), C.POINTER(McmcFused), _P, C.POINTER(PoseGrad),
-                                                  _P]),
-    "cugs_project_backward_adam_sparse": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
-                                               C.POINTER(AdamFused), _P, _P]),
-    "cugs_project_backward_adam_sparse_pose": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
-                                                    C.POINTER(AdamFused), _P, C.POINTER(PoseGrad), _P]),
+    "cugs_project_backward_opts": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F,
+                                        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ProjectionOpts), _P]),
+    "cugs_project_backward_adam_opts": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Camera), _F, _P,
+                                             C.POINTER(AdamFused), _P, C.POINTER(ProjectionOpts), _P]),
     "cugs_ply_vertex_floats": (_I, [_I, _I]),
     "cugs_ply_pack": (_I, [_L, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P]),
     "cugs_ply_unpack": (_I, [_L, _I, _I, _P, _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P]),

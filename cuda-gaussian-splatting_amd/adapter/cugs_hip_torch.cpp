@@ -305,28 +305,16 @@ ProjectionBackwardOutput project_backward_impl(const torch::Tensor* accum, const
     auto pos = f32c(positions), rot = f32c(rotations), scl = f32c(scales), opa = f32c(opacities), rad = radii.contiguous();
     auto cm = gm.defined() ? gm.contiguous() : gm, cc = gc.defined() ? gc.contiguous() : gc;
     auto cr = gr.defined() ? gr.contiguous() : gr, co = go.defined() ? go.contiguous() : go;
-    if (pose) {
-        check(cugs_project_backward_pose(n, static_cast<int>(sh.size(2)), degree, ptr<float>(pos), ptr<float>(rot),
-                                         ptr<float>(scl), ptr<float>(opa), ptr<float>(sh), ptr<int32_t>(rad),
-                                         colour_gate ? ptr<uint8_t>(*colour_gate) : nullptr, &camera, scale_modifier,
-                                         accum ? ptr<float>(*accum) : nullptr, ptr<float>(cm), ptr<float>(cc),
-                                         ptr<float>(cr), ptr<float>(co), ptr<float>(o.dL_dpositions),
-                                         ptr<float>(o.dL_drotations), ptr<float>(o.dL_dscales),
-                                         ptr<float>(o.dL_dopacities), ptr<float>(o.dL_dsh_coeffs),
-                                         d_means_out ? ptr<float>(*d_means_out) : nullptr,
-                                         /*dL_drgb_gated_out=*/nullptr, pose, stream_of(positions)),
-              "cugs_project_backward_pose");
-        return o;
-    }
-    check(cugs_project_backward(n, static_cast<int>(sh.size(2)), degree, ptr<float>(pos), ptr<float>(rot), ptr<float>(scl),
-                                ptr<float>(opa), ptr<float>(sh), ptr<int32_t>(rad),
-                                colour_gate ? ptr<uint8_t>(*colour_gate) : nullptr, &camera, scale_modifier,
-                                accum ? ptr<float>(*accum) : nullptr, ptr<float>(cm), ptr<float>(cc), ptr<float>(cr),
-                                ptr<float>(co), ptr<float>(o.dL_dpositions), ptr<float>(o.dL_drotations),
-                                ptr<float>(o.dL_dscales), ptr<float>(o.dL_dopacities), ptr<float>(o.dL_dsh_coeffs),
-                                d_means_out ? ptr<float>(*d_means_out) : nullptr, /*dL_drgb_gated_out=*/nullptr,
-                                stream_of(positions)),
-          "cugs_project_backward");
+    const cugs_projection_opts opts{nullptr, pose, 0};
+    check(cugs_project_backward_opts(n, static_cast<int>(sh.size(2)), degree, ptr<float>(pos), ptr<float>(rot),
+                                     ptr<float>(scl), ptr<float>(opa), ptr<float>(sh), ptr<int32_t>(rad),
+                                     colour_gate ? ptr<uint8_t>(*colour_gate) : nullptr, &camera, scale_modifier,
+                                     accum ? ptr<float>(*accum) : nullptr, ptr<float>(cm), ptr<float>(cc), ptr<float>(cr),
+                                     ptr<float>(co), ptr<float>(o.dL_dpositions), ptr<float>(o.dL_drotations),
+                                     ptr<float>(o.dL_dscales), ptr<float>(o.dL_dopacities), ptr<float>(o.dL_dsh_coeffs),
+                                     d_means_out ? ptr<float>(*d_means_out) : nullptr, /*dL_drgb_gated_out=*/nullptr,
+                                     &opts, stream_of(positions)),
+          "cugs_project_backward_opts");
     return o;
 }
 }  // namespace
@@ -562,65 +550,17 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                     "the fused optimizer step needs the colour_gate of cugs_hip::render");
         const cugs_adam_fused adam = fused->begin_fused_step();
         auto radii = ro.radii.contiguous(), gate = ro.colour_gate.contiguous();
-        if (mcmc) {
-            const cugs_mcmc_fused mc = mcmc->fused_args(step);
-            if (want_camera_grad) {
-                check(cugs_project_backward_adam_mcmc_pose(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
-                                                           ptr<float>(model.positions), ptr<float>(model.rotations),
-                                                           ptr<float>(model.scales), ptr<float>(model.opacities),
-                                                           ptr<float>(model.sh_coeffs), ptr<int32_t>(radii),
-                                                           ptr<uint8_t>(gate), &camera, settings.scale_modifier,
-                                                           ptr<float>(rb.grad_accum), &adam, &mc,
-                                                           ptr<float>(o.dL_dmeans_2d), &pose, stream_of(dL_dcolor)),
-                      "cugs_project_backward_adam_mcmc_pose");
-                return o;
-            }
-            check(cugs_project_backward_adam_mcmc(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
-                                                  ptr<float>(model.positions), ptr<float>(model.rotations),
-                                                  ptr<float>(model.scales), ptr<float>(model.opacities),
-                                                  ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate),
-                                                  &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam, &mc,
-                                                  ptr<float>(o.dL_dmeans_2d), stream_of(dL_dcolor)),
-                  "cugs_project_backward_adam_mcmc");
-            return o;
-        }
-        if (sparse_adam) {                                      // only the Gaussians this view sees
-            if (want_camera_grad) {
-                check(cugs_project_backward_adam_sparse_pose(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
-                                                             ptr<float>(model.positions), ptr<float>(model.rotations),
-                                                             ptr<float>(model.scales), ptr<float>(model.opacities),
-                                                             ptr<float>(model.sh_coeffs), ptr<int32_t>(radii),
-                                                             ptr<uint8_t>(gate), &camera, settings.scale_modifier,
-                                                             ptr<float>(rb.grad_accum), &adam, ptr<float>(o.dL_dmeans_2d),
-                                                             &pose, stream_of(dL_dcolor)),
-                      "cugs_project_backward_adam_sparse_pose");
-                return o;
-            }
-            check(cugs_project_backward_adam_sparse(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
-                                                    ptr<float>(model.positions), ptr<float>(model.rotations),
-                                                    ptr<float>(model.scales), ptr<float>(model.opacities),
-                                                    ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate),
-                                                    &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam,
-                                                    ptr<float>(o.dL_dmeans_2d), stream_of(dL_dcolor)),
-                  "cugs_project_backward_adam_sparse");
-            return o;
-        }
-        if (want_camera_grad) {
-            check(cugs_project_backward_adam_pose(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
-                                                  ptr<float>(model.positions), ptr<float>(model.rotations),
-                                                  ptr<float>(model.scales), ptr<float>(model.opacities),
-                                                  ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate),
-                                                  &camera, settings.scale_modifier, ptr<float>(rb.grad_accum), &adam,
-                                                  ptr<float>(o.dL_dmeans_2d), &pose, stream_of(dL_dcolor)),
-                  "cugs_project_backward_adam_pose");
-            return o;
-        }
-        check(cugs_project_backward_adam(n, static_cast<int>(model.sh_coeffs.size(2)), degree, ptr<float>(model.positions),
-                                         ptr<float>(model.rotations), ptr<float>(model.scales), ptr<float>(model.opacities),
-                                         ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate), &camera,
-                                         settings.scale_modifier, ptr<float>(rb.grad_accum), &adam,
-                                         ptr<float>(o.dL_dmeans_2d), stream_of(dL_dcolor)),
-              "cugs_project_backward_adam");
+        cugs_mcmc_fused mc{};
+        if (mcmc) mc = mcmc->fused_args(step);
+        // sparse_adam: only the Gaussians this view sees
+        const cugs_projection_opts opts{mcmc ? &mc : nullptr, want_camera_grad ? &pose : nullptr, sparse_adam ? 1 : 0};
+        check(cugs_project_backward_adam_opts(n, static_cast<int>(model.sh_coeffs.size(2)), degree,
+                                              ptr<float>(model.positions), ptr<float>(model.rotations),
+                                              ptr<float>(model.scales), ptr<float>(model.opacities),
+                                              ptr<float>(model.sh_coeffs), ptr<int32_t>(radii), ptr<uint8_t>(gate), &camera,
+                                              settings.scale_modifier, ptr<float>(rb.grad_accum), &adam,
+                                              ptr<float>(o.dL_dmeans_2d), &opts, stream_of(dL_dcolor)),
+              "cugs_project_backward_adam_opts");
         return o;
     }
     // without the gate bits (a RenderOutput that went through the reference's struct) the kernel recomputes the gate

@@ -118,7 +118,7 @@ RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const 
 class FusedAdam;
 class MCMCController;
 // `fused` (optional, not in the reference; single-GPU training): the projection backward applies the optimizer step to
-// the model in place (cugs_project_backward_adam) and the five parameter gradients are never materialised (undefined
+// the model in place (cugs_project_backward_adam_opts) and the five parameter gradients are never materialised (undefined
 // in the result; dL_dmeans_2d is returned) - bit for bit render_backward + apply_gradients + step.
 BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutput& render_out,
                                const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
@@ -126,11 +126,11 @@ BackwardOutput render_backward(const torch::Tensor& dL_dcolor, const RenderOutpu
                                const torch::Tensor& dL_ddepth_map = {}, const torch::Tensor& dL_dalpha = {},
                                bool want_camera_grad = false, bool want_abs_grad = false, bool sparse_adam = false);
 // `sparse_adam` (with `fused` only, never with `mcmc`; not in the reference): the fused step touches only
-// the Gaussians this view sees, render_out.radii > 0 (cugs_project_backward_adam_sparse / _sparse_pose) - bit for bit
+// the Gaussians this view sees, render_out.radii > 0 (cugs_projection_opts.sparse, with or without the camera gradient) - bit for bit
 // render_backward + apply_gradients + step(render_out.radii); every other Gaussian keeps parameters and moments and is
 // not read at all.
 // `mcmc` (with `fused` only): the regulariser gradient and the position noise of iteration `step` ride in
-// the same launch (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + compute_regularization's
+// the same launch (cugs_projection_opts.mcmc) - bit for bit render_backward, + compute_regularization's
 // gradients, apply_gradients, step, inject_noise(model, step).
 // `dL_ddepth_map`, `dL_dalpha` ([H,W] each, optional, not in the reference): the gradients of RenderOutput::depth_map
 // (needs render(..., want_depth_map = true)) and of the alpha map 1 - final_T, on every route above.
@@ -223,7 +223,7 @@ public:
     // corrections from the global step count, which advances by one whatever the mask); the others keep parameters and
     // moments bit for bit and are neither read nor written (cugs_fused_adam_groups_rows).
     void step(const torch::Tensor& visible);
-    // The optimizer half of cugs_project_backward_adam: counts the step, returns moments / learning rates / bias
+    // The optimizer half of cugs_project_backward_adam_opts: counts the step, returns moments / learning rates / bias
     // corrections for the launch that updates the parameters in place (they must be contiguous float32).
     cugs_adam_fused begin_fused_step();
     const std::array<torch::Tensor, 5>& params() const { return params_; }

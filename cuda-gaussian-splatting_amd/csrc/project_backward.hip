@@ -31,39 +31,6 @@ int launch_shv(int64_t n, int degree, const float* pos, const float* gated, cons
 
 
 template <int C>
-int launch_pb(int64_t n, int degree, const CamArgs& cam, const PBPtrs& p, bool aligned, hipStream_t st,
-              const AdamFusedArgs* adam = nullptr) {
-    const AdamFusedArgs none{};
-    if (adam) {
-        if constexpr (C == 16) {
-            if (aligned && p.colour_gate) {
-                hipLaunchKernelGGL((k_project_backward<C, true, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{}, PoseArgs{});
-                CUGS_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-        if (aligned)
-            hipLaunchKernelGGL((k_project_backward<C, true, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{}, PoseArgs{});
-        else
-            hipLaunchKernelGGL((k_project_backward<C, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, *adam, McmcFusedArgs{}, PoseArgs{});
-    } else if (aligned) {
-        if constexpr (C == 16) {
-            if (p.colour_gate) {
-                hipLaunchKernelGGL((k_project_backward<C, true, false, true>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{}, PoseArgs{});
-                CUGS_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-        hipLaunchKernelGGL((k_project_backward<C, true, false>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{}, PoseArgs{});
-    } else {
-        hipLaunchKernelGGL((k_project_backward<C, false, false>), dim3(grid_for(n)), dim3(CUGS_BLOCK), 0, st, n, degree, cam, p, none, McmcFusedArgs{}, PoseArgs{});
-    }
-    CUGS_LAUNCH_CHECK();
-    return 0;
-}
-
-
-template <int C>
 int launch_shb(int64_t n, int degree, const float* sh, const float* dirs, const float* g, float* out,
                bool aligned, hipStream_t st) {
     if (aligned)
@@ -74,8 +41,68 @@ int launch_shb(int64_t n, int degree, const float* sh, const float* dirs, const 
     return 0;
 }
 
+// Steps 3 to 7 of the sequence both entry points share (include/cugs_hip.h, cugs_projection_opts), behind the request's
+// own check and prepare_plain / prepare_adam, whose result is `prepared`.
+int finish_pb(int prepared, PBCall& c, const cugs_projection_opts& o) {
+    if (prepared < 0) return prepared;
+    if (o.pose) {
+        const int rp = cugs_pb_check_pose(c.n, o.pose);
+        if (rp != 0) return rp;
+    }
+    if (prepared == 1) return o.pose ? cugs_pb_pose_zeros(o.pose, c.st) : 0;
+    if (o.mcmc) {
+        const int rm = prepare_mcmc(c.n, o.mcmc, c.mc);
+        if (rm != 0) return rm;
+    }
+    c.mcmc = o.mcmc != nullptr;
+    c.pose_host = o.pose;
+    if (o.pose) c.pose = pose_args(o.pose);
+    if (o.sparse) return cugs_pb_launch_sparse(c);
+    if (o.pose) return cugs_pb_launch_pose(c);
+    if (o.mcmc) return cugs_pb_launch_mcmc(c);
+    return c.adam ? launch_pb<true, false, false, false>(c) : launch_pb<false, false, false, false>(c);
+}
 
 }  // namespace
+
+extern "C" int cugs_project_backward_opts(int64_t n, int num_coeffs, int active_degree, const float* positions,
+                                          const float* rotations, const float* scales, const float* opacities,
+                                          const float* sh_coeffs, const int32_t* radii, const uint8_t* colour_gate,
+                                          const cugs_camera* camera_host, float scale_modifier,
+                                          const float* grad_accum, const float* dL_dmeans_2d,
+                                          const float* dL_dcov_2d_inv, const float* dL_drgb,
+                                          const float* dL_dopacity_act, float* dL_dpositions, float* dL_drotations,
+                                          float* dL_dscales, float* dL_dopacities, float* dL_dsh_coeffs,
+                                          float* dL_dmeans_2d_out, float* dL_drgb_gated_out,
+                                          const cugs_projection_opts* opts, void* stream) {
+    const cugs_projection_opts o = opts ? *opts : cugs_projection_opts{};
+    if (o.mcmc || o.sparse) return CUGS_EINVAL;                   // options of the fused step
+    PBCall c{};
+    c.n = n; c.num_coeffs = num_coeffs; c.degree = active_degree; c.st = static_cast<hipStream_t>(stream);
+    const int r = prepare_plain(n, num_coeffs, active_degree, positions, rotations, scales, opacities, sh_coeffs, radii,
+                                colour_gate, camera_host, scale_modifier, grad_accum, dL_dmeans_2d, dL_dcov_2d_inv, dL_drgb,
+                                dL_dopacity_act, dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs,
+                                dL_dmeans_2d_out, dL_drgb_gated_out, c.cam, c.p, c.aligned);
+    return finish_pb(r, c, o);
+}
+
+extern "C" int cugs_project_backward_adam_opts(int64_t n, int num_coeffs, int active_degree, float* positions,
+                                               float* rotations, float* scales, float* opacities, float* sh_coeffs,
+                                               const int32_t* radii, const uint8_t* colour_gate,
+                                               const cugs_camera* camera_host, float scale_modifier,
+                                               const float* grad_accum, const cugs_adam_fused* adam_host,
+                                               float* dL_dmeans_2d_out, const cugs_projection_opts* opts,
+                                               void* stream) {
+    const cugs_projection_opts o = opts ? *opts : cugs_projection_opts{};
+    if (o.mcmc && o.sparse) return CUGS_EINVAL;                   // the regulariser and the noise act on every Gaussian
+    PBCall c{};
+    c.n = n; c.num_coeffs = num_coeffs; c.degree = active_degree; c.st = static_cast<hipStream_t>(stream);
+    c.adam = true;
+    const int r = prepare_adam(n, num_coeffs, active_degree, positions, rotations, scales, opacities, sh_coeffs, radii,
+                               colour_gate, camera_host, scale_modifier, grad_accum, adam_host, dL_dmeans_2d_out, c.cam, c.p,
+                               c.adam_args, c.aligned);
+    return finish_pb(r, c, o);
+}
 
 extern "C" int cugs_project_backward(int64_t n, int num_coeffs, int active_degree, const float* positions,
                                      const float* rotations, const float* scales, const float* opacities,
@@ -86,23 +113,11 @@ extern "C" int cugs_project_backward(int64_t n, int num_coeffs, int active_degre
                                      const float* dL_dopacity_act, float* dL_dpositions, float* dL_drotations,
                                      float* dL_dscales, float* dL_dopacities, float* dL_dsh_coeffs,
                                      float* dL_dmeans_2d_out, float* dL_drgb_gated_out, void* stream) {
-    CamArgs cam;
-    PBPtrs p;
-    bool aligned;
-    const int r = prepare_plain(n, num_coeffs, active_degree, positions, rotations, scales, opacities, sh_coeffs, radii,
-                                colour_gate, camera_host, scale_modifier, grad_accum, dL_dmeans_2d, dL_dcov_2d_inv, dL_drgb,
-                                dL_dopacity_act, dL_dpositions, dL_drotations, dL_dscales, dL_dopacities, dL_dsh_coeffs,
-                                dL_dmeans_2d_out, dL_drgb_gated_out, cam, p, aligned);
-    if (r != 0) return r == 1 ? 0 : r;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (num_coeffs) {
-        case 1: return launch_pb<1>(n, active_degree, cam, p, aligned, st);
-        case 4: return launch_pb<4>(n, active_degree, cam, p, aligned, st);
-        case 9: return launch_pb<9>(n, active_degree, cam, p, aligned, st);
-        default: return launch_pb<16>(n, active_degree, cam, p, aligned, st);
-    }
+    return cugs_project_backward_opts(n, num_coeffs, active_degree, positions, rotations, scales, opacities, sh_coeffs, radii,
+                                      colour_gate, camera_host, scale_modifier, grad_accum, dL_dmeans_2d, dL_dcov_2d_inv,
+                                      dL_drgb, dL_dopacity_act, dL_dpositions, dL_drotations, dL_dscales, dL_dopacities,
+                                      dL_dsh_coeffs, dL_dmeans_2d_out, dL_drgb_gated_out, nullptr, stream);
 }
-
 
 extern "C" int cugs_project_backward_adam(int64_t n, int num_coeffs, int active_degree, float* positions,
                                           float* rotations, float* scales, float* opacities, float* sh_coeffs,
@@ -110,21 +125,9 @@ extern "C" int cugs_project_backward_adam(int64_t n, int num_coeffs, int active_
                                           const cugs_camera* camera_host, float scale_modifier,
                                           const float* grad_accum, const cugs_adam_fused* adam_host,
                                           float* dL_dmeans_2d_out, void* stream) {
-    CamArgs cam;
-    PBPtrs p;
-    AdamFusedArgs a;
-    bool aligned;
-    const int r = prepare_adam(n, num_coeffs, active_degree, positions, rotations, scales, opacities, sh_coeffs, radii,
-                               colour_gate, camera_host, scale_modifier, grad_accum, adam_host, dL_dmeans_2d_out, cam, p,
-                               a, aligned);
-    if (r != 0) return r == 1 ? 0 : r;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (num_coeffs) {
-        case 1: return launch_pb<1>(n, active_degree, cam, p, aligned, st, &a);
-        case 4: return launch_pb<4>(n, active_degree, cam, p, aligned, st, &a);
-        case 9: return launch_pb<9>(n, active_degree, cam, p, aligned, st, &a);
-        default: return launch_pb<16>(n, active_degree, cam, p, aligned, st, &a);
-    }
+    return cugs_project_backward_adam_opts(n, num_coeffs, active_degree, positions, rotations, scales, opacities, sh_coeffs,
+                                           radii, colour_gate, camera_host, scale_modifier, grad_accum, adam_host,
+                                           dL_dmeans_2d_out, nullptr, stream);
 }
 
 extern "C" int cugs_evaluate_sh_backward(int degree, int64_t n, int num_coeffs, const float* sh_coeffs,

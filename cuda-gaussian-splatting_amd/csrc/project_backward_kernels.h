@@ -1,12 +1,56 @@
 // project_backward_kernels.h — the device code of the projection backward (k_project_backward and the kernels beside
-// it) and the fused Adam route's argument checks, shared by two translation units: project_backward.hip (every entry
-// point without MCMC) and project_backward_mcmc.hip (cugs_project_backward_adam_mcmc, N5).  The MCMC instantiations
-// of k_project_backward live in the second one: compiled into the same module they changed the register allocation
-// of the existing ADAM instantiations; apart, those compile to the same code as without N5.  The POSE instantiations
-// (project_backward_pose.hip) and the SPARSE ones (project_backward_sparse.hip) are kept apart in the same way.
+// it), its argument checks and its one launch template, shared by four translation units.  project_backward.hip holds
+// the public entry points (include/cugs_hip.h: cugs_project_backward_opts, cugs_project_backward_adam_opts) and the
+// instantiations without an option; the MCMC instantiations of k_project_backward live in project_backward_mcmc.hip:
+// compiled into the same module they changed the register allocation of the existing ADAM instantiations; apart, those
+// compile to the same code as without N5.  The POSE instantiations (project_backward_pose.hip) and the SPARSE ones
+// (project_backward_sparse.hip) are kept apart in the same way.  The entry points reach the other three files through
+// the host functions at the end of this header, over one call block (PBCall).
 #pragma once
 #include "cugs_raster_common.h"
 #include "cugs_mcmc.h"
+
+// ---- the kernel's argument blocks (outside the unnamed namespace: PBCall crosses translation units) ----
+struct PBPtrs {
+    const float* positions; const float* rotations; const float* scales; const float* opacities;
+    const float* sh; const int32_t* radii; const uint8_t* colour_gate;
+    const float* grad_accum;
+    const float* g_means; const float* g_cov; const float* g_rgb; const float* g_opa;
+    float* d_pos; float* d_rot; float* d_scl; float* d_opa; float* d_sh; float* d_means_out;
+    float* d_rgb_gated_out;      // [n,3] gated colour gradient (for the data-parallel exchange); may be NULL
+    // ADAM variant only: the parameters themselves, updated in place (d_pos .. d_sh are then unused)
+    float* w_pos; float* w_rot; float* w_scl; float* w_opa; float* w_sh;
+};
+
+// ADAM variant only (fused Adam, single-GPU training): moments, learning rates and constants of the step.
+struct AdamFusedArgs {
+    float* m[5]; float* v[5];          // ParamGroup order: positions, sh_coeffs, opacities, scales, rotations
+    float lr[5];
+    float beta1, beta2, eps, bc1, bc2;
+};
+
+// POSE variant only (project_backward_pose.hip, DESIGN.md 4.14): where the camera gradient goes.
+struct PoseArgs {
+    float* partial;     // [gridDim.x, 12] one fp32 partial per workgroup: dL/dW row-major, then dL/dtvec
+    float* rows;        // [n, 12] the per-Gaussian terms (tests), or NULL
+};
+constexpr int POSE_TERMS = 12;
+
+// One checked request, ready to launch: what the entry points hand to the translation unit that owns the kernels.
+// adam, mcmc and pose_host != NULL name the instantiation within that unit; the blocks of the options that are off
+// stay zero.
+struct PBCall {
+    int64_t n;
+    int num_coeffs, degree;
+    bool aligned, adam, mcmc;
+    const cugs_pose_grad* pose_host;    // NULL: no camera gradient
+    hipStream_t st;
+    CamArgs cam;
+    PBPtrs p;
+    AdamFusedArgs adam_args;
+    McmcFusedArgs mc;
+    PoseArgs pose;
+};
 
 namespace {
 
@@ -130,11 +174,6 @@ __device__ __forceinline__ void store_sh_rows(float* __restrict__ dst_base, int6
 // ---- fused Adam (single-GPU training: cugs_project_backward_adam) -------------------------------------------
 // k_fused_adam's per-element update (optimizer/fused_adam.cu:44-76) in the reference's operation order - the same
 // function adam.hip runs, so the fused and the two-kernel paths give identical bits.
-struct AdamFusedArgs {
-    float* m[5]; float* v[5];          // ParamGroup order: positions, sh_coeffs, opacities, scales, rotations
-    float lr[5];
-    float beta1, beta2, eps, bc1, bc2;
-};
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float lr, const AdamFusedArgs& h) {
     const float mi = h.beta1 * m + (1.0f - h.beta1) * g;
     m = mi;
@@ -360,24 +399,6 @@ __device__ __forceinline__ void add_grad_t_from_cov(const Sym2& g, const Sym3& S
             j5 * (2.0f * fy * t.y * tz_inv3);
 }
 
-struct PBPtrs {
-    const float* positions; const float* rotations; const float* scales; const float* opacities;
-    const float* sh; const int32_t* radii; const uint8_t* colour_gate;
-    const float* grad_accum;
-    const float* g_means; const float* g_cov; const float* g_rgb; const float* g_opa;
-    float* d_pos; float* d_rot; float* d_scl; float* d_opa; float* d_sh; float* d_means_out;
-    float* d_rgb_gated_out;      // [n,3] gated colour gradient (for the data-parallel exchange); may be NULL
-    // ADAM variant only: the parameters themselves, updated in place (d_pos .. d_sh are then unused)
-    float* w_pos; float* w_rot; float* w_scl; float* w_opa; float* w_sh;
-};
-
-// POSE variant only (project_backward_pose.hip, DESIGN.md 4.14): where the camera gradient goes.
-struct PoseArgs {
-    float* partial;     // [gridDim.x, 12] one fp32 partial per workgroup: dL/dW row-major, then dL/dtvec
-    float* rows;        // [n, 12] the per-Gaussian terms (tests), or NULL
-};
-constexpr int POSE_TERMS = 12;
-
 // The workgroup's sum of the twelve per-thread camera terms -> out[0..11]: reduce12r16 inside each DPP row, the four
 // rows of a wave by two xor shuffles, the CUGS_BLOCK / 64 waves through LDS in wave order.  `s_red` is the SH tile,
 // free once every thread has passed the barrier at the top (its last reader, the SH gradient rows, is done).  A fixed
@@ -404,7 +425,7 @@ __device__ __forceinline__ void pose_block_partial(const float (&v)[POSE_TERMS],
 // of gradient writes and as many reads by a separate optimizer launch disappear (472 of 2020 B at degree 3).
 // FACTORS (C == 16, aligned rows, the gate bits given, no fused optimizer step): the LDS tile holds the factors of the
 // gradient rows instead of the rows (store_sh_rows_from_factors); also the route without SH gradient rows at all.
-// MCMC (with ADAM only; cugs_project_backward_adam_mcmc): the per-iteration MCMC work of N5 rides along (cugs_mcmc.h) - the
+// MCMC (with ADAM only; cugs_projection_opts.mcmc): the per-iteration MCMC work of N5 rides along (cugs_mcmc.h) - the
 // regulariser gradient joins d_logit / d_log of every live Gaussian (radius 0 included: the reference adds it to the
 // whole gradient tensor), opacity and scales are stepped before the position, and the position noise, formed from the
 // UPDATED opacity and scales as cugs_mcmc_inject_noise forms it, joins the updated position.
@@ -811,7 +832,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_sh_backward_views(int64_t n, int
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + CUGS_BLOCK - 1) / CUGS_BLOCK); }
 
-// The argument checks and argument block of cugs_project_backward (and its POSE twin, project_backward_pose.hip).
+// The argument checks and argument block of cugs_project_backward_opts.
 // Returns 1 when there is nothing to launch (n == 0), else 0 or a CUGS_E* code.
 inline int prepare_plain(int64_t n, int num_coeffs, int active_degree, const float* positions, const float* rotations,
                          const float* scales, const float* opacities, const float* sh_coeffs, const int32_t* radii,
@@ -842,7 +863,7 @@ inline int prepare_plain(int64_t n, int num_coeffs, int active_degree, const flo
     return 0;
 }
 
-// The MCMC block of cugs_project_backward_adam_mcmc (and its POSE twin) for n > 0 Gaussians.
+// The MCMC block of cugs_project_backward_adam_opts for n > 0 Gaussians.
 inline int prepare_mcmc(int64_t n, const cugs_mcmc_fused* mcmc_host, McmcFusedArgs& mc) {
     if (n > 2147483647ll / 3) return CUGS_EOVERFLOW;
     mc.coef_o = mcmc_host->lambda_opacity / (float)n;            // the regulariser's mean, as cugs_mcmc_regularization
@@ -852,8 +873,13 @@ inline int prepare_mcmc(int64_t n, const cugs_mcmc_fused* mcmc_host, McmcFusedAr
     return 0;
 }
 
-// The argument checks and argument blocks of cugs_project_backward_adam / _mcmc (project_backward.hip,
-// project_backward_mcmc.hip).  Returns 1 when there is nothing to launch (n == 0), else 0 or a CUGS_E* code.
+// where the POSE launch over n Gaussians leaves its workgroup partials (the block has passed check_pose)
+inline PoseArgs pose_args(const cugs_pose_grad* pose) {
+    return PoseArgs{reinterpret_cast<float*>(pose->workspace), pose->rows};
+}
+
+// The argument checks and argument blocks of cugs_project_backward_adam_opts.
+// Returns 1 when there is nothing to launch (n == 0), else 0 or a CUGS_E* code.
 inline int prepare_adam(int64_t n, int num_coeffs, int active_degree, float* positions, float* rotations, float* scales,
                         float* opacities, float* sh_coeffs, const int32_t* radii, const uint8_t* colour_gate,
                         const cugs_camera* camera_host, float scale_modifier, const float* grad_accum,
@@ -881,4 +907,42 @@ inline int prepare_adam(int64_t n, int num_coeffs, int active_degree, float* pos
     return 0;
 }
 
+// The one launch of k_project_backward: storage C from num_coeffs; the factor tile for aligned degree-3 storage with the
+// gate bits, else the aligned kernel, else the unaligned one.  A translation unit instantiates it for the option
+// combinations whose kernels it owns, and for no other.
+template <bool ADAM, bool MCMC, bool POSE, bool SPARSE>
+int launch_pb(const PBCall& c) {
+    const auto launch = [&](auto* kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for(c.n)), dim3(CUGS_BLOCK), 0, c.st, c.n, c.degree, c.cam, c.p, c.adam_args,
+                           c.mc, c.pose);
+    };
+    const auto storage = [&](auto C) {
+        if constexpr (C() == 16) {
+            if (c.aligned && c.p.colour_gate) {
+                launch(k_project_backward<C(), true, ADAM, true, MCMC, POSE, SPARSE>);
+                return;
+            }
+        }
+        cugs_with_bool(c.aligned, [&](auto A) { launch(k_project_backward<C(), A(), ADAM, false, MCMC, POSE, SPARSE>); });
+    };
+    switch (c.num_coeffs) {
+        case 1: storage(std::integral_constant<int, 1>{}); break;
+        case 4: storage(std::integral_constant<int, 4>{}); break;
+        case 9: storage(std::integral_constant<int, 9>{}); break;
+        default: storage(std::integral_constant<int, 16>{}); break;
+    }
+    CUGS_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
+
+// ---- between the translation units (host functions, not exported) ----
+// Each launches the request on the kernels its file owns; the POSE ones add the reduction behind the launch.
+#define CUGS_PB_LOCAL __attribute__((visibility("hidden")))
+int cugs_pb_launch_mcmc(const PBCall& c) CUGS_PB_LOCAL;       // project_backward_mcmc.hip: adam, mcmc, no pose
+int cugs_pb_launch_pose(const PBCall& c) CUGS_PB_LOCAL;       // project_backward_pose.hip: pose; plain, adam or adam + mcmc
+int cugs_pb_launch_sparse(const PBCall& c) CUGS_PB_LOCAL;     // project_backward_sparse.hip: adam, sparse; with or without pose
+// project_backward_pose.hip: check_pose and pose_zeros of project_backward_pose_reduce.h, for the entry points
+int cugs_pb_check_pose(int64_t n, const cugs_pose_grad* pose) CUGS_PB_LOCAL;
+int cugs_pb_pose_zeros(const cugs_pose_grad* pose, hipStream_t st) CUGS_PB_LOCAL;

@@ -71,11 +71,6 @@ inline int check_pose(int64_t n, const cugs_pose_grad* pose) {
     return 0;
 }
 
-// where the POSE launch over n Gaussians leaves its workgroup partials
-inline PoseArgs pose_args(const cugs_pose_grad* pose) {
-    return PoseArgs{reinterpret_cast<float*>(pose->workspace), pose->rows};
-}
-
 // the two launches behind a POSE launch over n Gaussians: partials -> slices -> pose->dL_dview
 inline int pose_reduce(int64_t n, const cugs_pose_grad* pose, hipStream_t st) {
     char* ws = static_cast<char*>(pose->workspace);

@@ -105,7 +105,7 @@ class FusedAdam:
         return self.learning_rates_[int(group)]
 
     def begin_fused_step(self):
-        """The optimizer half of cugs_project_backward_adam (render_backward(..., fused_adam=self)): counts the
+        """The optimizer half of cugs_project_backward_adam_opts (render_backward(..., fused_adam=self)): counts the
         step and returns the C struct with the moments, learning rates and bias corrections.  The update itself
         happens inside the projection backward, on the model this optimizer was built for, which must be
         contiguous float32 (the kernel writes the parameters in place)."""

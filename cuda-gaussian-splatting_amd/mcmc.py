@@ -5,7 +5,7 @@ schedule.  N stays constant: nothing is reallocated and the optimizer is never r
 Per iteration the reference runs, on libtorch ops, the regulariser (an autograd pass and a host sync) before the
 optimizer step and the position noise after it.  Here they are one launch each - or none at all: with
 render_backward(..., fused_adam=opt, mcmc=controller, mcmc_step=step) both ride inside the projection backward's
-fused Adam step (cugs_project_backward_adam_mcmc), bit for bit the unfused sequence.
+fused Adam step (cugs_projection_opts.mcmc), bit for bit the unfused sequence.
 
 Differences from the reference, all at the boundary:
   * random draws (position noise, relocation jitter, relocation sampling) come from a counter-based Philox4x32-10

@@ -592,11 +592,8 @@ def project_backward(dL_dmeans_2d: Optional[torch.Tensor], dL_dcov_2d_inv: Optio
             _ptr(cont(grad_accum)), _ptr(cont(dL_dmeans_2d)), _ptr(cont(dL_dcov_2d_inv)), _ptr(cont(dL_drgb)),
             _ptr(cont(dL_dopacity_act)), _ptr(d_pos), _ptr(d_rot), _ptr(d_scl), _ptr(d_opa), _ptr(d_sh),
             _ptr(dL_dmeans_2d_out), _ptr(dL_drgb_gated_out))
-    if want_camera_grad:
-        pg = _pose_grad(d_view, dL_dview_rows, n, dev)
-        check(lib.cugs_project_backward_pose(*args, C.byref(pg), _stream(dev)), "cugs_project_backward_pose")
-    else:
-        check(lib.cugs_project_backward(*args, _stream(dev)), "cugs_project_backward")
+    opts = _lib.ProjectionOpts(pose=C.pointer(_pose_grad(d_view, dL_dview_rows, n, dev)) if want_camera_grad else None)
+    check(lib.cugs_project_backward_opts(*args, C.byref(opts), _stream(dev)), "cugs_project_backward_opts")
     return ProjectionBackwardOutput(d_pos, d_rot, d_scl, d_opa, d_sh, dL_dviewmat=d_view)
 
 
@@ -747,7 +744,7 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
     five parameter gradients are never materialised (they are None in the result; dL_dmeans_2d is returned).
     Equivalent, bit for bit, to render_backward + apply_gradients + step.
     `mcmc` (an MCMCController, with fused_adam only): the per-iteration MCMC work rides in the same launch
-    (cugs_project_backward_adam_mcmc) - bit for bit render_backward, + the gradients of
+    (cugs_projection_opts.mcmc) - bit for bit render_backward, + the gradients of
     mcmc.compute_regularization, apply_gradients, step, mcmc.inject_noise(model, mcmc_step, mcmc_noise).
     `dL_ddepth_map`, `dL_dalpha` ([H,W] each, optional, not in the reference): the gradients of
     RenderOutput.depth_map (needs render(..., want_depth_map=True)) and of RenderOutput.alpha.  They reach the
@@ -768,8 +765,8 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
     the rows alive): pass it to DensificationController.accumulate_gradients as it is.  Every other output is the same
     up to the order of the blend's atomic adds.  Without the flag the field is None and nothing changes.
     `sparse_adam=True` (with fused_adam only, never with mcmc; not in the reference): the fused step
-    touches only the Gaussians this view sees, render_out.radii > 0 (cugs_project_backward_adam_sparse, with
-    want_camera_grad cugs_project_backward_adam_sparse_pose).  A visible Gaussian is stepped exactly as the dense fused
+    touches only the Gaussians this view sees, render_out.radii > 0 (cugs_projection_opts.sparse, with or without
+    want_camera_grad).  A visible Gaussian is stepped exactly as the dense fused
     route steps it (bias corrections from the optimizer's global step count, which advances by one either way); every
     other Gaussian keeps parameters and moments bit for bit and is not read at all.  Equivalent, bit for bit, to
     render_backward + apply_gradients + step(visible=render_out.radii); dL_dmeans_2d, dL_dviewmat and dL_dmeans_2d_abs
@@ -840,26 +837,12 @@ def render_backward(dL_dcolor: torch.Tensor, render_out: RenderOutput, model: Ga
                 _ptr(render_out.colour_gate.contiguous()), C.byref(cam), float(settings.scale_modifier),
                 _ptr(rb.grad_accum), C.byref(adam))
         d_view = torch.empty((4, 4), **f) if want_camera_grad else None
-        pg = _pose_grad(d_view, None, n, dev) if want_camera_grad else None
-        if mcmc is not None:
-            mc = mcmc.fused_args(mcmc_step, mcmc_noise)
-            if pg is not None:
-                check(lib.cugs_project_backward_adam_mcmc_pose(*args, C.byref(mc), _ptr(d_means_2d), C.byref(pg),
-                                                               _stream(dev)), "cugs_project_backward_adam_mcmc_pose")
-            else:
-                check(lib.cugs_project_backward_adam_mcmc(*args, C.byref(mc), _ptr(d_means_2d), _stream(dev)),
-                      "cugs_project_backward_adam_mcmc")
-        elif sparse_adam and pg is not None:
-            check(lib.cugs_project_backward_adam_sparse_pose(*args, _ptr(d_means_2d), C.byref(pg), _stream(dev)),
-                  "cugs_project_backward_adam_sparse_pose")
-        elif sparse_adam:
-            check(lib.cugs_project_backward_adam_sparse(*args, _ptr(d_means_2d), _stream(dev)),
-                  "cugs_project_backward_adam_sparse")
-        elif pg is not None:
-            check(lib.cugs_project_backward_adam_pose(*args, _ptr(d_means_2d), C.byref(pg), _stream(dev)),
-                  "cugs_project_backward_adam_pose")
-        else:
-            check(lib.cugs_project_backward_adam(*args, _ptr(d_means_2d), _stream(dev)), "cugs_project_backward_adam")
+        opts = _lib.ProjectionOpts(
+            mcmc=C.pointer(mcmc.fused_args(mcmc_step, mcmc_noise)) if mcmc is not None else None,
+            pose=C.pointer(_pose_grad(d_view, None, n, dev)) if want_camera_grad else None,
+            sparse=1 if sparse_adam else 0)
+        check(lib.cugs_project_backward_adam_opts(*args, _ptr(d_means_2d), C.byref(opts), _stream(dev)),
+              "cugs_project_backward_adam_opts")
         return BackwardOutput(None, None, None, None, None, d_means_2d, dL_dviewmat=d_view,
                               dL_dmeans_2d_abs=rb.dL_dmeans_2d_abs)
     _torch_check(mcmc is None, "the fused MCMC route needs fused_adam (otherwise: compute_regularization, "

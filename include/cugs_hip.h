@@ -451,12 +451,7 @@ int cugs_fused_adam_groups(const cugs_adam_group* groups_host, int ngroups, floa
  * Hence for any mask: result = where(visible row, cugs_fused_adam_groups' result, value before), bit for bit.
  * One launch; a group with grad == NULL is skipped.  CUGS_EINVAL: ngroups > 8, a group with row_elems <= 0 or
  * n != row_elems * n_rows, radii == NULL with n_rows > 0; n_rows == 0 returns 0 and queues nothing.
- * cugs_project_backward_adam_sparse / _sparse_pose: cugs_project_backward_adam / _adam_pose under the same rule, with
- * the `radii` they are given anyway: a Gaussian with radii <= 0 is not read (no gradient row, no geometry, none of its
- * parameter and moment words), dL_dmeans_2d_out gets (0, 0) for it and dL_dview nothing from it, as on the dense
- * routes; every visible Gaussian is stepped exactly as the dense route steps it.  Same arguments, same checks, same
- * error codes as the dense entry points.  There is no sparse MCMC route: its regulariser and noise act on every
- * Gaussian. */
+ * The fused step under the same rule: cugs_projection_opts.sparse (cugs_project_backward_adam_opts, further down). */
 int cugs_fused_adam_groups_rows(const cugs_adam_group* groups_host, int ngroups, const int32_t* row_elems_host,
                                 const int32_t* radii, int64_t n_rows, float beta1, float beta2, float eps,
                                 float bc1, float bc2, void* stream);
@@ -729,9 +724,7 @@ int cugs_image_to_float(int src_width, int src_height, const uint8_t* src_rgb8, 
  *   source row of the j-th relocated row, j < num_relocated.  No host sync.  Workspace:
  *   cugs_mcmc_relocate_workspace_bytes(n).  cugs_mcmc_regularization needs cugs_mcmc_relocate_workspace_bytes(0)
  *   bytes (16 KB of partial sums) whatever n; a relocation workspace serves it too.
- * cugs_project_backward_adam_mcmc: cugs_project_backward_adam with the per-iteration MCMC work fused in, bit for
- *   bit the sequence regulariser (add) -> Adam step -> inject_noise: the regulariser gradient joins the opacity
- *   and scale gradients of every Gaussian, and the noise (from the updated opacity and scales) the updated position.
+ * cugs_mcmc_fused: the same work fused into the optimizer step (cugs_projection_opts.mcmc, further down).
  */
 #define CUGS_MCMC_STREAM_NOISE 0u
 #define CUGS_MCMC_STREAM_JITTER 1u
@@ -759,23 +752,11 @@ int cugs_mcmc_relocate(int64_t n, int num_coeffs, float* positions, float* rotat
                        float* sh_coeffs, float dead_threshold, float relocate_cap, float scene_extent, uint64_t seed,
                        uint32_t step, float* const m[5], float* const v[5], void* workspace, size_t workspace_bytes,
                        int32_t* stats, int32_t* src_out, void* stream);
-int cugs_project_backward_adam_mcmc(int64_t n, int num_coeffs, int active_degree, float* positions, float* rotations,
-                                    float* scales, float* opacities, float* sh_coeffs, const int32_t* radii,
-                                    const uint8_t* colour_gate, const cugs_camera* camera_host, float scale_modifier,
-                                    const float* grad_accum, const cugs_adam_fused* adam_host,
-                                    const cugs_mcmc_fused* mcmc_host, float* dL_dmeans_2d_out, void* stream);
 
-/* ---- camera pose gradient (not in the reference) ------------------------------------------------
- * cugs_project_backward_pose / _adam_pose / _adam_mcmc_pose: the entry point of the same name without `_pose`, bit for
- * bit in every output it has, plus dL/dview, the gradient with respect to cugs_camera.view: t = W p + tvec with
- * W = view[0..2][0..2], tvec[r] = view[r*4+3].  Per live Gaussian with radii > 0 and an invertible Sigma':
- * dL/dtvec = dt (the gradient of its camera-space position, depth-map word included) and dL/dW = dt (x) p + J^T K
- * (K = dL/d(J W)); every other Gaussian adds 0.  The SH view direction is held constant (as dL_dpositions holds it).
+/* ---- the camera gradient's block (not in the reference): see cugs_projection_opts.pose ----
  * dL_dview: device float[16] in the layout of cugs_camera.view, row 3 written 0.  rows: optional device [n,12], each
  * Gaussian's dL/dW (row-major) then dL/dtvec; NULL in production.  workspace: cugs_pose_grad_workspace_bytes(n)
- * device bytes, 16-byte aligned.  The workgroup partials are summed in fp64 in a fixed order by two more launches on
- * `stream` and rounded once: the same bits from run to run, no host sync.  CUGS_EINVAL for a NULL pose_host or
- * dL_dview, CUGS_EWORKSPACE for a workspace that is too small, before anything is queued; n == 0 writes 16 zeros. */
+ * device bytes, 16-byte aligned. */
 typedef struct cugs_pose_grad {
     float* dL_dview;
     float* rows;
@@ -783,7 +764,38 @@ typedef struct cugs_pose_grad {
     size_t workspace_bytes;
 } cugs_pose_grad;
 size_t cugs_pose_grad_workspace_bytes(int64_t n);
-int cugs_project_backward_pose(int64_t n, int num_coeffs, int active_degree,
+
+/* ---- the projection backward with options ----------------------------------------------------------------------
+ * cugs_project_backward_opts / cugs_project_backward_adam_opts: cugs_project_backward / cugs_project_backward_adam
+ * (further up; the same arguments, checks and results) with one block of options in front of `stream`.  opts == NULL or
+ * an all-zero block: exactly those two, which are this call with NULL.  A non-NULL block pointer switches its option on.
+ * In this order, before anything is queued:
+ *   1. the request: CUGS_EINVAL for mcmc or sparse on cugs_project_backward_opts, and for mcmc together with sparse;
+ *   2. the checks of the entry point without options;
+ *   3. with pose: CUGS_EINVAL for a NULL dL_dview and, for n > 0, a NULL workspace, CUGS_EWORKSPACE for one that is
+ *      too small, CUGS_EALIGN for a misaligned one;
+ *   4. n == 0: nothing is queued but, with pose, the 16 zeros of dL_dview;
+ *   5. with mcmc: CUGS_EOVERFLOW for 3 n > INT32_MAX. */
+typedef struct cugs_projection_opts {
+    /* Fused entry only.  The per-iteration MCMC work of N5 rides in the launch, bit for bit the sequence regulariser
+     * (add) -> Adam step -> inject_noise: the regulariser gradient joins the opacity and scale gradients of every
+     * Gaussian, and the noise (from the updated opacity and scales) the updated position. */
+    const cugs_mcmc_fused* mcmc;
+    /* Either entry.  Every output the call has without it, bit for bit, plus dL/dview, the gradient with respect to
+     * cugs_camera.view: t = W p + tvec with W = view[0..2][0..2], tvec[r] = view[r*4+3].  Per live Gaussian with
+     * radii > 0 and an invertible Sigma': dL/dtvec = dt (the gradient of its camera-space position, depth-map word
+     * included) and dL/dW = dt (x) p + J^T K (K = dL/d(J W)); every other Gaussian adds 0.  The SH view direction is
+     * held constant (as dL_dpositions holds it).  The workgroup partials are summed in fp64 in a fixed order by two
+     * more launches on `stream` and rounded once: the same bits from run to run, no host sync. */
+    const cugs_pose_grad* pose;
+    /* Fused entry only, non-zero = on; not together with mcmc, whose regulariser and noise act on every Gaussian.
+     * Sparse Adam (the block beside cugs_fused_adam_groups_rows above) with the `radii` the call is
+     * given anyway: a Gaussian with radii <= 0 is not read (no gradient row, no geometry, none of its parameter and
+     * moment words), dL_dmeans_2d_out gets (0, 0) for it and dL_dview nothing from it, as on the dense route; every
+     * visible Gaussian is stepped exactly as the dense route steps it, bit for bit. */
+    int sparse;
+} cugs_projection_opts;
+int cugs_project_backward_opts(int64_t n, int num_coeffs, int active_degree,
                                const float* positions, const float* rotations, const float* scales,
                                const float* opacities, const float* sh_coeffs, const int32_t* radii,
                                const uint8_t* colour_gate, const cugs_camera* camera_host,
@@ -792,34 +804,13 @@ int cugs_project_backward_pose(int64_t n, int num_coeffs, int active_degree,
                                const float* dL_drgb, const float* dL_dopacity_act,
                                float* dL_dpositions, float* dL_drotations, float* dL_dscales,
                                float* dL_dopacities, float* dL_dsh_coeffs, float* dL_dmeans_2d_out,
-                               float* dL_drgb_gated_out, const cugs_pose_grad* pose_host, void* stream);
-int cugs_project_backward_adam_pose(int64_t n, int num_coeffs, int active_degree, float* positions,
+                               float* dL_drgb_gated_out, const cugs_projection_opts* opts, void* stream);
+int cugs_project_backward_adam_opts(int64_t n, int num_coeffs, int active_degree, float* positions,
                                     float* rotations, float* scales, float* opacities, float* sh_coeffs,
                                     const int32_t* radii, const uint8_t* colour_gate,
                                     const cugs_camera* camera_host, float scale_modifier,
                                     const float* grad_accum, const cugs_adam_fused* adam_host,
-                                    float* dL_dmeans_2d_out, const cugs_pose_grad* pose_host, void* stream);
-int cugs_project_backward_adam_mcmc_pose(int64_t n, int num_coeffs, int active_degree, float* positions,
-                                         float* rotations, float* scales, float* opacities, float* sh_coeffs,
-                                         const int32_t* radii, const uint8_t* colour_gate,
-                                         const cugs_camera* camera_host, float scale_modifier,
-                                         const float* grad_accum, const cugs_adam_fused* adam_host,
-                                         const cugs_mcmc_fused* mcmc_host, float* dL_dmeans_2d_out,
-                                         const cugs_pose_grad* pose_host, void* stream);
-
-/* The fused routes of sparse Adam (semantics: the sparse Adam block beside cugs_fused_adam_groups_rows above). */
-int cugs_project_backward_adam_sparse(int64_t n, int num_coeffs, int active_degree, float* positions,
-                                      float* rotations, float* scales, float* opacities, float* sh_coeffs,
-                                      const int32_t* radii, const uint8_t* colour_gate,
-                                      const cugs_camera* camera_host, float scale_modifier,
-                                      const float* grad_accum, const cugs_adam_fused* adam_host,
-                                      float* dL_dmeans_2d_out, void* stream);
-int cugs_project_backward_adam_sparse_pose(int64_t n, int num_coeffs, int active_degree, float* positions,
-                                           float* rotations, float* scales, float* opacities, float* sh_coeffs,
-                                           const int32_t* radii, const uint8_t* colour_gate,
-                                           const cugs_camera* camera_host, float scale_modifier,
-                                           const float* grad_accum, const cugs_adam_fused* adam_host,
-                                           float* dL_dmeans_2d_out, const cugs_pose_grad* pose_host, void* stream);
+                                    float* dL_dmeans_2d_out, const cugs_projection_opts* opts, void* stream);
 
 /* ---- init_gaussians_from_sparse (core/gaussian_init.cpp:25-152) on the device ----------------------------------
  * The reference turns a point cloud into a model on the CPU: positions copied, the DC coefficient from the colour

@@ -272,6 +272,7 @@ def test_fused_route_equals_unfused_sequence(pkg, dev, deg, explicit):
                                              lambda_opacity=0.05, lambda_scale=0.05, seed=77), 5.0)
     R = pkg.rasterizer
     P = lambda t: C.c_void_p(t.data_ptr())
+    from cugs_amd import _lib
     from cugs_amd._lib import check, lib
     for step in range(1, 4):
         out = pkg.render(ma, cam, settings)
@@ -294,10 +295,11 @@ def test_fused_route_equals_unfused_sequence(pkg, dev, deg, explicit):
         mc = ctrl.fused_args(step, noise)
         dm_b = torch.empty((n, 2), device=dev)
         cam_abi = cam.to_abi()
-        check(lib.cugs_project_backward_adam_mcmc(n, int(mb.sh_coeffs.shape[2]), deg, P(mb.positions), P(mb.rotations),
+        opts = _lib.ProjectionOpts(mcmc=C.pointer(mc))
+        check(lib.cugs_project_backward_adam_opts(n, int(mb.sh_coeffs.shape[2]), deg, P(mb.positions), P(mb.rotations),
                                                   P(mb.scales), P(mb.opacities), P(mb.sh_coeffs), P(out.radii),
                                                   P(out.colour_gate), C.byref(cam_abi), float(settings.scale_modifier),
-                                                  P(rb.grad_accum), C.byref(adam), C.byref(mc), P(dm_b),
+                                                  P(rb.grad_accum), C.byref(adam), P(dm_b), C.byref(opts),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), "fused mcmc")
         assert torch.equal(dm_a, dm_b)
         for i, k in enumerate(NAMES):

@@ -141,13 +141,15 @@ def test_empty_model_gives_zeros(pkg, dev):
     adam = _lib.AdamFused()
     mc = _lib.McmcFused()
     P = C.c_void_p
-    assert lib.cugs_project_backward_pose(0, 16, 3, *([None] * 7), C.byref(abi), 1.0, *([None] * 12), C.byref(pg),
+    opts = _lib.ProjectionOpts(pose=C.pointer(pg))
+    assert lib.cugs_project_backward_opts(0, 16, 3, *([None] * 7), C.byref(abi), 1.0, *([None] * 12), C.byref(opts),
                                           None) == 0
     torch.cuda.synchronize()
     assert torch.equal(view, torch.zeros(4, 4, device=dev))
-    for fn, extra in ((lib.cugs_project_backward_adam_pose, ()), (lib.cugs_project_backward_adam_mcmc_pose, (C.byref(mc),))):
+    for opts in (_lib.ProjectionOpts(pose=C.pointer(pg)), _lib.ProjectionOpts(mcmc=C.pointer(mc), pose=C.pointer(pg))):
         view.fill_(7.0)
-        assert fn(0, 16, 3, *([None] * 7), C.byref(abi), 1.0, None, C.byref(adam), *extra, P(0), C.byref(pg), None) == 0
+        assert lib.cugs_project_backward_adam_opts(0, 16, 3, *([None] * 7), C.byref(abi), 1.0, None, C.byref(adam), P(0),
+                                                   C.byref(opts), None) == 0
         torch.cuda.synchronize()
         assert torch.equal(view, torch.zeros(4, 4, device=dev))
 
@@ -190,13 +192,8 @@ def _fused(pkg, dev, arrays, cam, out, accum, route, pose):
     ws = torch.empty(lib.cugs_pose_grad_workspace_bytes(n), dtype=torch.uint8, device=dev)
     pg = _lib.PoseGrad(view.data_ptr(), None, ws.data_ptr(), ws.numel()) if pose else None
     mc = _lib.McmcFused(0.01, 0.01, 5e5, 100.0, 0.005, 3, 1234, None)
-    if route == "mcmc":
-        rc = (lib.cugs_project_backward_adam_mcmc_pose(*args, C.byref(mc), P(d_means), C.byref(pg), None) if pose else
-              lib.cugs_project_backward_adam_mcmc(*args, C.byref(mc), P(d_means), None))
-    else:
-        rc = (lib.cugs_project_backward_adam_pose(*args, P(d_means), C.byref(pg), None) if pose else
-              lib.cugs_project_backward_adam(*args, P(d_means), None))
-    assert rc == 0
+    opts = _lib.ProjectionOpts(mcmc=C.pointer(mc) if route == "mcmc" else None, pose=C.pointer(pg) if pose else None)
+    assert lib.cugs_project_backward_adam_opts(*args, P(d_means), C.byref(opts), None) == 0
     torch.cuda.synchronize()
     return model, m + v, d_means, view
 

@@ -1,5 +1,5 @@
 """Sparse Adam on the GPU: FusedAdam.step(visible=) over cugs_fused_adam_groups_rows and
-render_backward(..., fused_adam=, sparse_adam=True) over cugs_project_backward_adam_sparse / _sparse_pose.
+render_backward(..., fused_adam=, sparse_adam=True) over cugs_project_backward_adam_opts with cugs_projection_opts.sparse.
 
 Everything is compared BIT FOR BIT: a visible row takes exactly the dense update of this step, an invisible row keeps
 its bits, so  sparse = where(visible row, dense step result, value before)  for the five parameter tensors and the ten
@@ -163,10 +163,10 @@ def _misaligned(t):
                                                       (600, 96, 64, 2, 2, True), (600, 96, 64, 2, 2, False),
                                                       (600, 96, 64, 3, 3, False)])
 def test_fused_sparse_equals_backward_then_masked_step(pkg, dev, n, w, h, deg, stored, aligned):
-    """Path A: project_backward -> apply_gradients -> step(visible=radii).  Path B: cugs_project_backward_adam_sparse.
+    """Path A: project_backward -> apply_gradients -> step(visible=radii).  Path B: the fused entry with sparse = 1.
     Same accumulator rows; model, moments and dL_dmeans_2d equal bit for bit over three steps, and path B's
     dL_dmeans_2d is the dense fused route's."""
-    from cugs_amd._lib import check, lib
+    from cugs_amd._lib import ProjectionOpts, check, lib
     arrays, cam, inv = _pattern_scene(pkg, n, w, h, stored, seed=n)
     settings = pkg.RenderSettings(background=[0.2, 0.1, 0.3], active_sh_degree=deg)
     g = torch.from_numpy(pkg.scene.make_dl_dcolor(w, h, seed=n + 1) * 3000.0).to(dev)
@@ -196,12 +196,12 @@ def test_fused_sparse_equals_backward_then_masked_step(pkg, dev, n, w, h, deg, s
                                               pb.dL_dsh_coeffs, dm_a))
         oa.step(visible=out.radii)
         cam_abi = cam.to_abi()
-        for fn, m, o, dm in ((lib.cugs_project_backward_adam_sparse, mb, ob, dm_b),
-                             (lib.cugs_project_backward_adam, mc, oc, dm_c)):
+        for sparse, m, o, dm in ((1, mb, ob, dm_b), (0, mc, oc, dm_c)):
             adam = o.begin_fused_step()
-            check(fn(n, int(m.sh_coeffs.shape[2]), deg, P(m.positions), P(m.rotations), P(m.scales), P(m.opacities),
-                     P(m.sh_coeffs), P(out.radii), P(out.colour_gate), C.byref(cam_abi), float(settings.scale_modifier),
-                     P(rb.grad_accum), C.byref(adam), P(dm), st()), "fused")
+            check(lib.cugs_project_backward_adam_opts(
+                n, int(m.sh_coeffs.shape[2]), deg, P(m.positions), P(m.rotations), P(m.scales), P(m.opacities),
+                P(m.sh_coeffs), P(out.radii), P(out.colour_gate), C.byref(cam_abi), float(settings.scale_modifier),
+                P(rb.grad_accum), C.byref(adam), P(dm), C.byref(ProjectionOpts(sparse=sparse)), st()), "fused")
         assert _bits_equal(dm_a, dm_b) and _bits_equal(dm_b, dm_c)
         got = _state(mb, ob)
         for i, (a, b) in enumerate(zip(_state(ma, oa), got)):

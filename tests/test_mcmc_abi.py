@@ -3,7 +3,11 @@ CUGS_EINVAL (-1) while n == 0 is a successful no-op (0), before anything touches
 import ctypes as C
 
 NAMES = ("cugs_mcmc_random_bits", "cugs_mcmc_regularization", "cugs_mcmc_inject_noise",
-         "cugs_mcmc_relocate_workspace_bytes", "cugs_mcmc_relocate", "cugs_project_backward_adam_mcmc")
+         "cugs_mcmc_relocate_workspace_bytes", "cugs_mcmc_relocate", "cugs_project_backward_opts",
+         "cugs_project_backward_adam_opts")
+GONE = ("cugs_project_backward_pose", "cugs_project_backward_adam_pose", "cugs_project_backward_adam_mcmc",
+        "cugs_project_backward_adam_mcmc_pose", "cugs_project_backward_adam_sparse",
+        "cugs_project_backward_adam_sparse_pose")            # now options of the two entries above
 
 
 def test_mcmc_symbols_exported_and_bound(pkg):
@@ -12,12 +16,15 @@ def test_mcmc_symbols_exported_and_bound(pkg):
     for n in NAMES:
         assert hasattr(lib, n), n
         assert n in _lib.SIGNATURES, n
+    for n in GONE:
+        assert not hasattr(lib, n), n
+        assert n not in _lib.SIGNATURES, n
     assert hasattr(pkg, "MCMCController") and hasattr(pkg, "MCMCConfig") and hasattr(pkg, "MCMCStats")
     assert C.sizeof(_lib.McmcFused) == 40
 
 
 def test_mcmc_argument_validation(pkg):
-    from cugs_amd._lib import AdamFused, Camera, McmcFused, lib
+    from cugs_amd._lib import AdamFused, Camera, McmcFused, ProjectionOpts, lib
     null = C.c_void_p(0)
     fake = C.c_void_p(0x1000)
     # generator
@@ -53,9 +60,17 @@ def test_mcmc_argument_validation(pkg):
                                   fake, null, null) == -1                   # m without v
     # fused route
     cam, adam, mc = Camera(), AdamFused(), McmcFused()
-    pb = lambda n, mcp: lib.cugs_project_backward_adam_mcmc(n, 16, 3, null, null, null, null, null, null, null,
-                                                            C.byref(cam), 1.0, null, C.byref(adam), mcp, null, null)
-    assert pb(-1, C.byref(mc)) == -1
-    assert pb(0, C.byref(mc)) == 0
-    assert pb(10, C.byref(mc)) == -1                                        # null pointers with n > 0
-    assert pb(0, None) == -1                                                # no MCMC arguments
+    with_mc = ProjectionOpts(mcmc=C.pointer(mc))
+    head = lambda n: (n, 16, 3, null, null, null, null, null, null, null, C.byref(cam), 1.0, null)
+    pb = lambda n, opts: lib.cugs_project_backward_adam_opts(*head(n), C.byref(adam), null,
+                                                             None if opts is None else C.byref(opts), null)
+    plain = lambda n, opts: lib.cugs_project_backward_opts(*head(n), *([null] * 11), C.byref(opts), null)
+    assert pb(-1, with_mc) == -1
+    assert pb(0, with_mc) == 0
+    assert pb(10, with_mc) == -1                                            # null pointers with n > 0
+    # no options: the dense fused step
+    assert pb(0, None) == 0 == lib.cugs_project_backward_adam(*head(0), C.byref(adam), null, null)
+    # requests that no kernel serves, refused before anything else is looked at (n == 0 would return 0)
+    assert plain(0, with_mc) == -1                                          # MCMC on the entry without the optimizer step
+    assert pb(0, ProjectionOpts(mcmc=C.pointer(mc), sparse=1)) == -1        # MCMC steps every Gaussian
+    assert plain(0, ProjectionOpts(sparse=1)) == -1                         # sparse on the entry without the optimizer step

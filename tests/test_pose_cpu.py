@@ -115,12 +115,21 @@ def test_apply_se3_composes_on_the_left_in_float64(pkg):
     assert abs(pkg.pose.rotation_angle_deg(moved.rotation, cam.rotation) - np.degrees(np.linalg.norm(xi[3:]))) < 1e-4
 
 
+def _opts(pose, mc=None):
+    """cugs_projection_opts over a PoseGrad (or None: no block at all) and an McmcFused (or None)."""
+    from cugs_amd import _lib
+    if pose is None and mc is None:
+        return None
+    return C.byref(_lib.ProjectionOpts(mcmc=None if mc is None else C.pointer(mc),
+                                       pose=None if pose is None else C.pointer(pose)))
+
+
 def _plain(lib, pose, n=10, camera=True):
     from cugs_amd import _lib
     cam = _lib.Camera()
-    return lib.cugs_project_backward_pose(n, 16, 3, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE,
+    return lib.cugs_project_backward_opts(n, 16, 3, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE,
                                           C.byref(cam) if camera else None, 1.0, FAKE, NUL, NUL, NUL, NUL,
-                                          FAKE, FAKE, FAKE, FAKE, FAKE, NUL, NUL, pose, NUL)
+                                          FAKE, FAKE, FAKE, FAKE, FAKE, NUL, NUL, _opts(pose), NUL)
 
 
 def _adam(lib, pose, mcmc=False, n=10):
@@ -130,18 +139,19 @@ def _adam(lib, pose, mcmc=False, n=10):
     for g in range(5):
         adam.m[g] = adam.v[g] = FAKE.value
     args = (n, 16, 3, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, C.byref(cam), 1.0, FAKE, C.byref(adam))
-    if mcmc:
-        mc = _lib.McmcFused()
-        return lib.cugs_project_backward_adam_mcmc_pose(*args, C.byref(mc), NUL, pose, NUL)
-    return lib.cugs_project_backward_adam_pose(*args, NUL, pose, NUL)
+    return lib.cugs_project_backward_adam_opts(*args, NUL, _opts(pose, _lib.McmcFused() if mcmc else None), NUL)
 
 
 def test_pose_symbols_bound(pkg):
     from cugs_amd import _lib
-    for name in ("cugs_pose_grad_workspace_bytes", "cugs_project_backward_pose", "cugs_project_backward_adam_pose",
-                 "cugs_project_backward_adam_mcmc_pose"):
+    for name in ("cugs_pose_grad_workspace_bytes", "cugs_project_backward_opts", "cugs_project_backward_adam_opts"):
         assert name in _lib.SIGNATURES
         assert getattr(C.CDLL(pkg.LIB_PATH), name)
+    for name in ("cugs_project_backward_pose", "cugs_project_backward_adam_pose", "cugs_project_backward_adam_mcmc",
+                 "cugs_project_backward_adam_mcmc_pose", "cugs_project_backward_adam_sparse",
+                 "cugs_project_backward_adam_sparse_pose"):          # now options of the two entries above
+        assert name not in _lib.SIGNATURES
+        assert not hasattr(C.CDLL(pkg.LIB_PATH), name)
 
 
 def test_pose_workspace_bytes(pkg):
@@ -163,10 +173,10 @@ def test_pose_entry_points_validate_before_queueing(pkg):
     no_ws = _lib.PoseGrad(FAKE.value, None, None, need)
     for call in (lambda p, **k: _plain(lib, p, **k), lambda p, **k: _adam(lib, p, **k),
                  lambda p, **k: _adam(lib, p, mcmc=True, **k)):
-        assert call(None, n=n) == EINVAL                        # no pose block
-        assert call(C.byref(no_out), n=n) == EINVAL             # no dL_dview
-        assert call(C.byref(no_ws), n=n) == EINVAL              # no workspace
-        assert call(C.byref(small), n=n) == EWORKSPACE          # one byte short
-        assert call(None, n=0) == EINVAL                        # checked before the n == 0 early out
-        assert call(C.byref(ok), n=-1) == EINVAL
-    assert _plain(lib, C.byref(ok), camera=False) == EINVAL
+        assert call(no_out, n=n) == EINVAL                      # no dL_dview
+        assert call(no_ws, n=n) == EINVAL                       # no workspace
+        assert call(small, n=n) == EWORKSPACE                   # one byte short
+        assert call(no_out, n=0) == EINVAL                      # checked before the n == 0 early out
+        assert call(None, n=0) == 0                             # no pose block: the entry without the camera gradient
+        assert call(ok, n=-1) == EINVAL
+    assert _plain(lib, ok, camera=False) == EINVAL

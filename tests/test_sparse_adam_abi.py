@@ -5,7 +5,10 @@ import ctypes as C
 import inspect
 
 EINVAL, EALIGN = -1, -2
-NAMES = ("cugs_fused_adam_groups_rows", "cugs_project_backward_adam_sparse", "cugs_project_backward_adam_sparse_pose")
+NAMES = ("cugs_fused_adam_groups_rows", "cugs_project_backward_opts", "cugs_project_backward_adam_opts")
+GONE = ("cugs_project_backward_pose", "cugs_project_backward_adam_pose", "cugs_project_backward_adam_mcmc",
+        "cugs_project_backward_adam_mcmc_pose", "cugs_project_backward_adam_sparse",
+        "cugs_project_backward_adam_sparse_pose")            # now options of the two entries above
 FAKE = 0x10000            # 16-byte aligned, never dereferenced: every call below returns before a launch
 
 
@@ -15,6 +18,9 @@ def test_sparse_symbols_exported_and_bound(pkg):
     for n in NAMES:
         assert hasattr(lib, n), n
         assert n in _lib.SIGNATURES, n
+    for n in GONE:
+        assert not hasattr(lib, n), n
+        assert n not in _lib.SIGNATURES, n
     assert "visible" in inspect.signature(pkg.FusedAdam.step).parameters
     assert inspect.signature(pkg.render_backward).parameters["sparse_adam"].default is False
 
@@ -70,7 +76,7 @@ def test_masked_step_argument_validation(pkg):
 
 
 def _fused(pkg, pose):
-    from cugs_amd._lib import AdamFused, Camera, PoseGrad, lib
+    from cugs_amd._lib import AdamFused, Camera, PoseGrad, ProjectionOpts, lib
     cam = Camera()
 
     def call(n=10, c=16, deg=3, model=FAKE, radii=FAKE, gate=FAKE, accum=FAKE, adam="ok", camera=True, pg="ok"):
@@ -82,11 +88,11 @@ def _fused(pkg, pose):
                                                           C.byref(cam) if camera else None, 1.0, C.c_void_p(accum), adam_p,
                                                           C.c_void_p(FAKE)]
         if not pose:
-            return lib.cugs_project_backward_adam_sparse(*args, None)
+            return lib.cugs_project_backward_adam_opts(*args, C.byref(ProjectionOpts(sparse=1)), None)
         p = PoseGrad()
-        p.dL_dview, p.workspace = FAKE, FAKE
+        p.dL_dview, p.workspace = FAKE if pg == "ok" else None, FAKE
         p.workspace_bytes = lib.cugs_pose_grad_workspace_bytes(n)
-        return lib.cugs_project_backward_adam_sparse_pose(*args, C.byref(p) if pg == "ok" else None, None)
+        return lib.cugs_project_backward_adam_opts(*args, C.byref(ProjectionOpts(pose=C.pointer(p), sparse=1)), None)
     return call
 
 
@@ -102,7 +108,7 @@ def test_fused_sparse_argument_validation(pkg):
         assert call(model=0) == EINVAL and call(gate=0) == EINVAL and call(camera=False) == EINVAL
         assert call(n=-1) == EINVAL and call(c=5) == EINVAL and call(deg=4) == EINVAL and call(c=4, deg=2) == EINVAL
         if pose:
-            assert call(pg=None) == EINVAL
+            assert call(pg=None) == EINVAL                   # a pose block without dL_dview
         else:
             assert call(n=0, model=0, radii=0, gate=0, accum=0) == 0     # an empty model queues nothing
     # the dense entry point answers the same

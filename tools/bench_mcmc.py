@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times SURVEY §8(f) N5 (MCMC densification) on one MI355X:
   (a) config 4 (6 M Gaussians, SH 3, 1600x1063): the fused projection backward + Adam step with and without MCMC
-      (cugs_project_backward_adam vs cugs_project_backward_adam_mcmc on the same accumulator rows);
+      (cugs_project_backward_adam_opts without and with cugs_projection_opts.mcmc on the same accumulator rows);
   (b) the stand-alone noise and regulariser kernels against the reference's libtorch op sequence
       (mcmc_densification.cpp:144-186, restated below) on the same GPU;
   (c) one relocation at 1 M and 6 M (cap 5 %) against the reference's op sequence (:56-138)."""
@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
 
 pkg = ge.load_package()
-from cugs_amd._lib import check, lib
+from cugs_amd._lib import ProjectionOpts, check, lib
 
 dev = torch.device("cuda:0")
 cfg = pkg.MCMCConfig(noise_lr_init=1e-3, noise_lr_final=1e-4)
@@ -111,8 +111,9 @@ def main():
             P(out.colour_gate), C.byref(cam_abi), 1.0, P(rb.grad_accum))
     adam = opt.begin_fused_step()
     mc = ctrl.fused_args(100)
-    plain = lambda: check(lib.cugs_project_backward_adam(*base, C.byref(adam), P(dm), st), "adam")
-    fused = lambda: check(lib.cugs_project_backward_adam_mcmc(*base, C.byref(adam), C.byref(mc), P(dm), st), "mcmc")
+    opts = ProjectionOpts(mcmc=C.pointer(mc))
+    plain = lambda: check(lib.cugs_project_backward_adam_opts(*base, C.byref(adam), P(dm), None, st), "adam")
+    fused = lambda: check(lib.cugs_project_backward_adam_opts(*base, C.byref(adam), P(dm), C.byref(opts), st), "mcmc")
     t_plain, t_fused = gpu_ms(plain, 30), gpu_ms(fused, 30)
     t_plain2 = gpu_ms(plain, 30)
     print("(a) config 4 projection backward + Adam: %.3f ms | with MCMC %.3f ms (%+.1f %%) | again without %.3f ms"

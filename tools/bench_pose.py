@@ -66,10 +66,11 @@ def run(name, rounds, per_round, warmup):
     adam_args = (n, 16, 3, P(model.positions), P(model.rotations), P(model.scales), P(model.opacities),
                  P(model.sh_coeffs), P(out.radii), P(out.colour_gate), C.byref(abi), 1.0, P(accum), C.byref(adam),
                  P(d[5]))
-    stage = timed([lambda: lib.cugs_project_backward(*plain_args, st),
-                   lambda: lib.cugs_project_backward_pose(*plain_args, C.byref(pg), st),
-                   lambda: lib.cugs_project_backward_adam(*adam_args, st),
-                   lambda: lib.cugs_project_backward_adam_pose(*adam_args, C.byref(pg), st)], rounds, per_round, warmup)
+    opts = _lib.ProjectionOpts(pose=C.pointer(pg))
+    stage = timed([lambda: lib.cugs_project_backward_opts(*plain_args, None, st),
+                   lambda: lib.cugs_project_backward_opts(*plain_args, C.byref(opts), st),
+                   lambda: lib.cugs_project_backward_adam_opts(*adam_args, None, st),
+                   lambda: lib.cugs_project_backward_adam_opts(*adam_args, C.byref(opts), st)], rounds, per_round, warmup)
 
     def step(want):
         o = pkg.render(model, cam, settings)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times sparse Adam on one MI355X, on the config-4 model and view (6 M Gaussians, SH 3, 1600x1063):
-  fused       cugs_project_backward_adam (dense) vs cugs_project_backward_adam_sparse on the same accumulator rows;
+  fused       cugs_project_backward_adam_opts dense vs cugs_projection_opts.sparse on the same accumulator rows;
   stand-alone cugs_fused_adam_groups (dense) vs cugs_fused_adam_groups_rows on the same five gradient tensors,
 for visible fractions 1.0, 0.5 and 0.1, the invisible rows one contiguous block or scattered (a random subset).  Rows
 are made invisible by negating their z; x and y are shrunk by 0.9 first so that no other Gaussian is culled and the
@@ -68,6 +68,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_sparse_adam: needs a GPU (there is no CPU fallback)")
     pkg = ge.load_package()
+    from cugs_amd import _lib
     from cugs_amd._lib import AdamGroup, check, lib
     dev = torch.device("cuda:0")
     n, w, h = args.n, 1600, 1063
@@ -115,9 +116,10 @@ def main():
         for i in range(5):
             adam.lr[i] = 1e-6                                    # many launches on one view: keep the model where it is
         base = (n, 16, 3, P(m.positions), P(m.rotations), P(m.scales), P(m.opacities), P(m.sh_coeffs), P(out.radii),
-                P(out.colour_gate), C.byref(cam_abi), 1.0, P(rb.grad_accum), C.byref(adam), P(dm), st)
-        dense = lambda: check(lib.cugs_project_backward_adam(*base), "dense")
-        sparse = lambda: check(lib.cugs_project_backward_adam_sparse(*base), "sparse")
+                P(out.colour_gate), C.byref(cam_abi), 1.0, P(rb.grad_accum), C.byref(adam), P(dm))
+        opts = _lib.ProjectionOpts(sparse=1)
+        dense = lambda: check(lib.cugs_project_backward_adam_opts(*base, None, st), "dense")
+        sparse = lambda: check(lib.cugs_project_backward_adam_opts(*base, C.byref(opts), st), "sparse")
         hyper = (0.9, 0.999, 1e-15, adam.bc1, adam.bc2, st)
         dense_s = lambda: check(lib.cugs_fused_adam_groups(groups, 5, *hyper), "dense step")
         sparse_s = lambda: check(lib.cugs_fused_adam_groups_rows(groups, 5, row_elems, P(out.radii), n, *hyper), "rows")
