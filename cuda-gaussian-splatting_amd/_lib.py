@@ -97,6 +97,23 @@ class NormalLossOpts(C.Structure):
                 ("min_alpha", C.c_float)]
 
 
+class TsdfVolume(C.Structure):
+    """struct cugs_tsdf_volume."""
+    _fields_ = [("planes", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("color", C.c_int32),
+                ("origin", C.c_float * 3), ("voxel_size", C.c_float), ("trunc", C.c_float)]
+
+
+class TsdfView(C.Structure):
+    """struct cugs_tsdf_view."""
+    _fields_ = [("camera", Camera), ("depth_map", C.c_void_p), ("alpha", C.c_void_p), ("color", C.c_void_p),
+                ("weight", C.c_void_p)]
+
+
+class TsdfOpts(C.Structure):
+    """struct cugs_tsdf_opts."""
+    _fields_ = [("min_depth", C.c_float), ("min_alpha", C.c_float), ("max_weight", C.c_float)]
+
+
 class BilagridDims(C.Structure):
     """struct cugs_bilagrid_dims."""
     _fields_ = [("l", C.c_int32), ("gy", C.c_int32), ("gx", C.c_int32)]
@@ -193,6 +210,10 @@ SIGNATURES = {
     "cugs_knn_workspace_bytes": (C.c_size_t, [_L, _I]),
     "cugs_knn_mean_distances": (_I, [_L, _I, _P, _P, _P, C.c_size_t, _I, _P]),
     "cugs_init_from_points": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cugs_tsdf_integrate": (_I, [C.POINTER(TsdfVolume), C.POINTER(TsdfView), _I, C.POINTER(TsdfOpts), _P]),
+    "cugs_mesh_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "cugs_mesh_plan": (_I, [C.POINTER(TsdfVolume), _F, _P, C.c_size_t, C.POINTER(C.c_int64), _P]),
+    "cugs_mesh_emit": (_I, [C.POINTER(TsdfVolume), _P, C.c_size_t, _L, _L, _P, _P, _P, _P]),
     "cugs_device_count": (_I, [C.POINTER(C.c_int)]),
 }
 

@@ -751,6 +751,81 @@ NormalLoss normal_loss(const torch::Tensor& depth_map, const torch::Tensor& alph
     return o;
 }
 
+TsdfVolume make_tsdf_volume(const float origin[3], int nx, int ny, int nz, float voxel_size, float trunc, bool color,
+                            const torch::Device& device, float max_weight, float min_depth) {
+    TORCH_CHECK(nx > 0 && ny > 0 && nz > 0, "the voxel counts must be positive, got ", nx, ", ", ny, ", ", nz);
+    TORCH_CHECK(static_cast<int64_t>(nx) * ny * nz <= 2147483647ll, "the volume does not fit 2^31 - 1 voxels");
+    TORCH_CHECK(device.is_cuda(), "a TsdfVolume lives on a CUDA device");
+    TsdfVolume v;
+    v.planes = torch::zeros({color ? 5 : 2, nz, ny, nx}, torch::TensorOptions().dtype(torch::kFloat32).device(device));
+    v.planes[0].fill_(1.0f);
+    for (int k = 0; k < 3; ++k) v.origin[k] = origin[k];
+    v.voxel_size = voxel_size; v.trunc = trunc; v.max_weight = max_weight; v.min_depth = min_depth;
+    return v;
+}
+
+static cugs_tsdf_volume tsdf_abi(const TsdfVolume& volume) {
+    const auto& p = volume.planes;
+    TORCH_CHECK(p.defined() && p.dim() == 4 && (p.size(0) == 2 || p.size(0) == 5), "planes must be [2 or 5, nz, ny, nx]");
+    TORCH_CHECK(p.dtype() == torch::kFloat32 && p.is_cuda() && p.is_contiguous(), "planes must be contiguous float32 on a CUDA device");
+    cugs_tsdf_volume v{};
+    v.planes = p.data_ptr<float>();
+    v.nx = static_cast<int32_t>(p.size(3)); v.ny = static_cast<int32_t>(p.size(2)); v.nz = static_cast<int32_t>(p.size(1));
+    v.color = p.size(0) == 5;
+    for (int k = 0; k < 3; ++k) v.origin[k] = volume.origin[k];
+    v.voxel_size = volume.voxel_size; v.trunc = volume.trunc;
+    return v;
+}
+
+void tsdf_integrate(TsdfVolume& volume, const std::vector<TsdfViewInput>& views, float min_alpha) {
+    const cugs_tsdf_volume vol = tsdf_abi(volume);
+    TORCH_CHECK(min_alpha > 0.0f && std::isfinite(min_alpha), "min_alpha must be positive and finite, got ", min_alpha);
+    cugs_tsdf_opts opts{};
+    opts.min_depth = volume.min_depth; opts.min_alpha = min_alpha; opts.max_weight = volume.max_weight;
+    constexpr size_t kMaxViews = 16;
+    for (size_t first = 0; first < views.size(); first += kMaxViews) {
+        const size_t n = std::min(kMaxViews, views.size() - first);
+        std::vector<cugs_tsdf_view> table(n);
+        std::vector<torch::Tensor> keep;                     // the contiguous maps, alive until the launch is queued
+        for (size_t i = 0; i < n; ++i) {
+            const TsdfViewInput& in = views[first + i];
+            const int64_t h = in.camera.height, w = in.camera.width;
+            auto map = [&](const torch::Tensor& t, const char* name, bool rgb) -> const float* {
+                TORCH_CHECK(t.defined() && t.dim() == (rgb ? 3 : 2) && t.size(0) == h && t.size(1) == w && (!rgb || t.size(2) == 3),
+                            name, " must be [H, W", rgb ? ", 3" : "", "] of the view's camera, got ", t.sizes());
+                TORCH_CHECK(t.dtype() == torch::kFloat32, name, " must be float32, got ", t.dtype());
+                TORCH_CHECK(t.is_cuda() && t.device() == volume.planes.device(), name, " must be on the volume's device");
+                keep.push_back(t.contiguous());
+                return keep.back().data_ptr<float>();
+            };
+            cugs_tsdf_view& v = table[i];
+            v.camera = in.camera;
+            v.depth_map = map(in.depth_map, "depth_map", false);
+            v.alpha = map(in.alpha, "alpha", false);
+            v.color = volume.has_color() ? map(in.color, "color", true) : nullptr;
+            v.weight = in.weight.defined() ? map(in.weight, "weight", false) : nullptr;
+        }
+        check(cugs_tsdf_integrate(&vol, table.data(), static_cast<int>(n), &opts, stream_of(volume.planes)), "cugs_tsdf_integrate");
+    }
+}
+
+Mesh mesh_extract(const TsdfVolume& volume, float min_weight) {
+    const cugs_tsdf_volume vol = tsdf_abi(volume);
+    TORCH_CHECK(min_weight >= 0.0f && std::isfinite(min_weight), "min_weight must be non-negative and finite, got ", min_weight);
+    const auto dev = volume.planes.device();
+    const size_t bytes = std::max<size_t>(cugs_mesh_workspace_bytes(vol.nx, vol.ny, vol.nz), 256);
+    auto ws = torch::empty({static_cast<int64_t>(bytes)}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+    int64_t counts[2] = {0, 0};
+    check(cugs_mesh_plan(&vol, min_weight, ws.data_ptr(), bytes, counts, stream_of(volume.planes)), "cugs_mesh_plan");
+    Mesh m;
+    m.vertices = torch::empty({counts[0], 3}, fopt(volume.planes));
+    m.faces = torch::empty({counts[1], 3}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+    if (volume.has_color()) m.colors = torch::empty({counts[0], 3}, fopt(volume.planes));
+    check(cugs_mesh_emit(&vol, ws.data_ptr(), bytes, counts[0], counts[1], ptr<float>(m.vertices), ptr<float>(m.colors),
+                         ptr<int32_t>(m.faces), stream_of(volume.planes)), "cugs_mesh_emit");
+    return m;
+}
+
 torch::Tensor depth_to_normals(const torch::Tensor& depth_map, const torch::Tensor& alpha, float fx, float fy, float cx,
                                float cy, float min_alpha) {
     return normal_loss(depth_map, alpha, fx, fy, cx, cy, {}, {}, 1.0f, 0.0f, min_alpha, false, true).normals;

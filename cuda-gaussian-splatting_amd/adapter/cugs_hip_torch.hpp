@@ -190,6 +190,30 @@ NormalLoss normal_loss(const torch::Tensor& depth_map, const torch::Tensor& alph
 torch::Tensor depth_to_normals(const torch::Tensor& depth_map, const torch::Tensor& alpha, float fx, float fy, float cx,
                                float cy, float min_alpha = 1e-3f);
 
+// Not in the reference: mesh export.  A dense truncated signed distance volume over torch::Tensor -
+// planes float32 [P, nz, ny, nx] (tsdf in units of trunc, weight, and with colour r, g, b; P = 5 or 2), voxel (0,0,0)
+// centred on `origin` - fused from render()'s depth and alpha maps by tsdf_integrate (up to 16 views per pass over the
+// volume, the views in the order given, the same bits however they are batched) and turned into a surface-net mesh by
+// mesh_extract (vertices float32 [V,3], faces int32 [F,3] with normals towards free space, colours float32 [V,3] or
+// undefined; one host sync for the two counts).  The rules are in include/cugs_hip.h.
+struct TsdfVolume {
+    torch::Tensor planes;
+    float origin[3] = {0.0f, 0.0f, 0.0f};
+    float voxel_size = 0.0f, trunc = 0.0f, max_weight = 64.0f, min_depth = 0.05f;
+    bool has_color() const { return planes.size(0) == 5; }
+};
+TsdfVolume make_tsdf_volume(const float origin[3], int nx, int ny, int nz, float voxel_size, float trunc, bool color,
+                            const torch::Device& device, float max_weight = 64.0f, float min_depth = 0.05f);
+struct TsdfViewInput {
+    cugs_camera camera;
+    torch::Tensor depth_map, alpha;     // float32 [H,W]
+    torch::Tensor color;                // float32 [H,W,3]; needed by a volume with colour
+    torch::Tensor weight;               // float32 [H,W]; undefined: all ones
+};
+void tsdf_integrate(TsdfVolume& volume, const std::vector<TsdfViewInput>& views, float min_alpha = 0.5f);
+struct Mesh { torch::Tensor vertices, faces, colors; };
+Mesh mesh_extract(const TsdfVolume& volume, float min_weight = 0.0f);
+
 // Not in the reference: per-view bilateral-grid colour correction.  grid: float32 [12, L, GY, GX],
 // contiguous, each extent in [2, 64], coefficient 4 i + j = row i, column j of [A | b]; images float32 [H,W,3] on the
 // grid's device.  bilagrid_slice: corrected = A(p) rendered(p) + b(p), the transform sampled trilinearly at

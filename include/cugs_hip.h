@@ -842,6 +842,89 @@ int cugs_init_from_points(int64_t n, int num_coeffs, const float* positions, con
                           const float* mean_dist, float* out_positions, float* out_sh, float* out_opacities,
                           float* out_rotations, float* out_scales, void* stream);
 
+/* ---- Mesh export: TSDF fusion of rendered depth and surface-net extraction (not in the reference) ----
+ * The volume: a dense box of nx x ny x nz voxels, x fastest; origin = the world position of the centre of voxel (0,0,0);
+ * one DEVICE array of float planes [P, nz, ny, nx]: plane 0 the tsdf in units of trunc (initially 1), plane 1 the weight
+ * (initially 0), and with color != 0 planes 2-4 r, g, b (initially 0); P = 5 with colour, 2 without.
+ *
+ * cugs_tsdf_integrate fuses num_views (1..16) views in ONE pass over the volume: each voxel is loaded once, updated by
+ * the views in the order given and stored once if any view touched it; a voxel no view touches moves no volume bytes;
+ * 16 views in one call leave the bits of 16 calls of one view.  A view: its camera (row-major view matrix v0..v11,
+ * pinhole, image size W x H), depth_map D and alpha A (DEVICE float[H*W], the maps render() returns), optional color
+ * (DEVICE float[H,W,3]) and optional per-pixel weight (DEVICE float[H*W]).  The fp32 rule per voxel (ix, iy, iz) and
+ * view, every step one correctly rounded operation:
+ *   1. px = ox + (float)ix * vs,  py, pz likewise
+ *   2. xc = ((v0 px + v1 py) + v2 pz) + v3,  yc from v4..v7, zc from v8..v11;  skip unless zc > min_depth
+ *   3. u = (fx xc) / zc + cx,  v = (fy yc) / zc + cy;  iu = floorf(u), iv = floorf(v) (pixel i covers [i, i+1));
+ *      skip unless 0 <= iu < W and 0 <= iv < H, tested on the floored FLOATS
+ *   4. pix = iv W + iu;  A = alpha[pix];  skip unless A > min_alpha;  d = D[pix] / A
+ *   5. w = weight[pix], or 1 without a weight map;  skip unless w > 0 (NaN skips)
+ *   6. sdf = d - zc;  skip unless sdf >= -trunc (a NaN depth skips);  tn = fminf(sdf / trunc, 1)
+ *   7. Wn = Wo + w;  T = (Wo To + w tn) / Wn;  each colour plane likewise from color[3 pix + ch];  W = fminf(Wn, max_weight)
+ * Every decision comes before the load that depends on it; no index is formed from a value that failed its test.
+ * 16-byte accesses (four x-neighbours per plane) where planes is 16-byte aligned and nx % 4 == 0, 4-byte accesses
+ * otherwise: the same bits either way.  One launch, the view table as a kernel argument; no atomics, no host sync, no
+ * allocation.  All checks before anything is queued, in this order: CUGS_EINVAL for a NULL vol, views or opts, a
+ * non-positive nx, ny or nz, num_views outside 1..16, NULL planes, voxel_size or trunc not positive and finite,
+ * min_depth, min_alpha or max_weight not positive and finite, then per view in order: fx or fy not positive and finite,
+ * a non-positive image size, a NULL depth_map or alpha, colour planes and no color; CUGS_EOVERFLOW for
+ * nx ny nz > 2^31 - 1.
+ *
+ * Surface nets.  A corner is valid where weight > min_weight and inside where tsdf < 0.  Cell (cx, cy, cz),
+ * 0 <= c < n - 1, is active when all eight corners are valid and their signs differ.  Corner k of a cell is the voxel
+ * (cx + (k & 1), cy + ((k >> 1) & 1), cz + (k >> 2)).
+ *   Vertices: one per active cell, in ascending cell index (x fastest).  Over the cell's twelve edges (a, b) in the fixed
+ *   order - the four along x (a = 0, 2, 4, 6), the four along y (a = 0, 1, 4, 5), the four along z (a = 0, 1, 2, 3),
+ *   b = a + (1 << axis) - whose ends differ in sign: t = fa / (fa - fb), the crossing = corner a's local coordinates with
+ *   t on the edge's axis; m = (the crossings added in that order, per component) / (float)count;
+ *   vertex = origin + ((float)c + m) * vs.  Colours: ca + t (cb - ca) per channel, added and divided the same way.
+ *   Faces: the lattice edge from voxel (x, y, z) to its +axis neighbour belongs to cell (x, y, z).  With the other two
+ *   axes (b, c) = (axis + 1, axis + 2) mod 3, the four cells around it are at offsets (-1,-1), (0,-1), (0,0), (-1,0) on
+ *   (b, c): q0..q3, counter-clockwise seen from +axis.  If the ends differ in sign and all four cells exist and are
+ *   active, the edge gives the triangles (q0,q1,q2), (q0,q2,q3) when the edge runs from negative to positive tsdf and
+ *   (q3,q2,q1), (q3,q1,q0) otherwise: the normal points from negative to positive tsdf, out of the surface.  Faces come
+ *   in ascending order of the owning cell, within a cell the edges along x, y, z, within an edge the two triangles;
+ *   int32 [F,3] of vertex indices.
+ * cugs_mesh_workspace_bytes: scratch for a volume (6 bytes per cell rounded up to chunks of 1024 cells, 8 bytes per
+ * chunk, 16 per 256 chunks; a multiple of 256; 0 for a non-positive size or nx ny nz > 2^31 - 1).
+ * cugs_mesh_plan classifies and scans (four launches) and blocks on one 16-byte read-back: counts_host = {vertices,
+ * faces}.  A volume without cells (an axis of one voxel) plans {0, 0} with nothing queued.
+ * cugs_mesh_emit writes vertices [V,3], optional colors [V,3] (colour planes needed) and faces [F,3] for the counts and
+ * the workspace of the plan (two launches; zero counts queue nothing); it never writes past V or F rows.
+ * Integer scans only, no float atomics: the same bytes from run to run.
+ * Checks, before anything is queued, in this order: CUGS_EINVAL for a NULL vol, non-positive nx, ny or nz, NULL planes,
+ * voxel_size or trunc not positive and finite, a NULL workspace, then (plan) a min_weight that is negative or not finite
+ * or a NULL counts_host, (emit) a negative count, a NULL vertices with V > 0 or faces with F > 0, colors without colour
+ * planes; CUGS_EOVERFLOW for nx ny nz > 2^31 - 1; CUGS_EWORKSPACE for a short workspace; CUGS_EALIGN for a workspace
+ * that is not 16-byte aligned; (emit) CUGS_EINVAL for counts no plan of this volume can give (V > cells, F > 6 cells). */
+typedef struct cugs_tsdf_volume {
+    float*  planes;         /* DEVICE float[P, nz, ny, nx] */
+    int32_t nx, ny, nz;
+    int32_t color;          /* 0: P = 2;  otherwise P = 5 */
+    float   origin[3];
+    float   voxel_size;     /* > 0 and finite */
+    float   trunc;          /* > 0 and finite */
+} cugs_tsdf_volume;
+typedef struct cugs_tsdf_view {
+    cugs_camera  camera;
+    const float* depth_map; /* DEVICE float[H*W] */
+    const float* alpha;     /* DEVICE float[H*W] */
+    const float* color;     /* DEVICE float[H,W,3]; needed with colour planes, ignored without */
+    const float* weight;    /* DEVICE float[H*W]; NULL: all ones */
+} cugs_tsdf_view;
+typedef struct cugs_tsdf_opts {
+    float min_depth;        /* > 0 and finite */
+    float min_alpha;        /* > 0 and finite */
+    float max_weight;       /* > 0 and finite */
+} cugs_tsdf_opts;
+int cugs_tsdf_integrate(const cugs_tsdf_volume* vol, const cugs_tsdf_view* views, int num_views,
+                        const cugs_tsdf_opts* opts, void* stream);
+size_t cugs_mesh_workspace_bytes(int nx, int ny, int nz);
+int cugs_mesh_plan(const cugs_tsdf_volume* vol, float min_weight, void* workspace, size_t workspace_bytes,
+                   int64_t* counts_host /* HOST int64[2] */, void* stream);
+int cugs_mesh_emit(const cugs_tsdf_volume* vol, void* workspace, size_t workspace_bytes, int64_t num_vertices,
+                   int64_t num_faces, float* vertices, float* colors /* nullable */, int32_t* faces, void* stream);
+
 /* Device properties the host side needs without linking the HIP runtime itself. */
 int cugs_device_count(int* count_host);
 
