@@ -10,12 +10,13 @@
 //
 // The cull is CONSERVATIVE and therefore invisible in the results: a record is dropped for a wave
 // only when alpha < 1/255 is certain for all 64 pixel centres, with a margin that covers the
-// fp32 rounding of the per-pixel power (see the derivation at may_touch_quad).  The per-pixel
+// fp32 rounding of the per-pixel power (see the derivation in cugs_blend_cull.h).  The per-pixel
 // path itself (pixel_alpha) follows DESIGN.md's FMA placement contract and cugs_detmath.h, so
 // every skip / clamp / termination decision equals the oracle's bit for bit.
 #pragma once
 
 #include "cugs_gaussian_math.h"
+#include "cugs_blend_cull.h"      // after the HIP runtime's qualifiers are defined
 
 #include <type_traits>
 
@@ -46,14 +47,30 @@ static inline void cugs_with_bool(bool flag, F&& f) {
     else f(std::false_type{});
 }
 
+// The cull (cugs_blend_cull.h: derivation, slack, NaN behaviour) on the LDS record.  Its per-record half runs when the
+// record is staged: cugs_stage_cull replaces word 6 of the geometry chunks (r0, r1) - tau = ln(255 o) in the packed
+// record - by cugs_cull_limit for the tile centred at (tile_cx, tile_cy) = 16 * tile + 8; only may_touch_quad reads
+// that word.  may_touch_quad, per (wave, record): can the Gaussian reach alpha >= 1/255 at ANY pixel centre of the
+// rectangle of centres [qx0, qx0+wx] x [qy0, qy0+wy] (the wave's quad, or the bounding box of its pixels that are still
+// active: ActiveRect below)?  `false` only when certainly not.
+__device__ __forceinline__ void cugs_stage_cull(const float4& r0, float4& r1, float tile_cx, float tile_cy) {
+    r1.z = cugs_cull_limit(r0.x, r0.y, r0.z, r0.w, r1.x, r1.z, tile_cx, tile_cy);
+}
+__device__ __forceinline__ bool may_touch_quad(float4 r0, float4 r1, float qx0, float qy0,
+                                               float wx, float wy) {
+    return cugs_cull_may_touch(r0.x, r0.y, r0.z, r0.w, r1.x, r1.z, qx0, qy0, wx, wy);
+}
+
 // Stage list entry `li` (if < end) into LDS slot threadIdx.x.  The LDS copy of the record carries the
 // Gaussian index (as bits) in its spare word 7, so that the backward's scatter address comes
 // with the same 16-byte read as the opacity.  Returns the Gaussian index (or -1).
 // DEPTH (depth-map kernels): word 9 of the LDS copy - 0 in the colour chunk (r, 0, g, b) - takes
 // depths[g], so that (r, z) is an aligned pair next to (g, b).  The packed HBM record is not changed.
+// Word 6 of the LDS copy - tau in the packed record - takes the cull's limit for the tile centred at (tile_cx, tile_cy)
+// (cugs_stage_cull): the per-record half of the cull, once per staged record instead of once per wave and test.
 template <bool PACKED, bool DEPTH = false>
-__device__ __forceinline__ int stage_record(const RasterSrc& s, int li, int end, float4* s_rec,
-                                            const float* __restrict__ depths = nullptr) {
+__device__ __forceinline__ int stage_record(const RasterSrc& s, int li, int end, float4* s_rec, float tile_cx,
+                                            float tile_cy, const float* __restrict__ depths = nullptr) {
     if (li >= end) return -1;
     const int g = s.gidx[li];
     float4 r0, r1, r2;
@@ -67,54 +84,12 @@ __device__ __forceinline__ int stage_record(const RasterSrc& s, int li, int end,
         r2 = make_float4(s.rgb[g * 3 + 0], 0.0f, s.rgb[g * 3 + 1], s.rgb[g * 3 + 2]);
     }
     r1.w = __int_as_float(g);
+    cugs_stage_cull(r0, r1, tile_cx, tile_cy);
     if (DEPTH) r2.y = depths[g];
     s_rec[threadIdx.x * CUGS_REC_F4 + 0] = r0;
     s_rec[threadIdx.x * CUGS_REC_F4 + 1] = r1;
     s_rec[threadIdx.x * CUGS_REC_F4 + 2] = r2;
     return g;
-}
-
-// Can the Gaussian in (r0, r1: the record's geometry chunks) reach alpha >= 1/255 at ANY pixel centre of the rectangle of
-// centres [qx0, qx0+wx] x [qy0, qy0+wy] (the wave's quad, or the bounding box of its pixels that are
-// still active: ActiveRect below)?  `false` only when certainly not.
-//
-// alpha = min(0.99, o * exp(power)) >= 1/255 needs -power <= tau := ln(255 o)  (tau < 0: never;
-// the record stores tau = -1 for o < 1/255, where o * exp(power <= 0) <= o < 1/255 exactly).
-// -power = q/2 with q(d) = a dx^2 + 2 b dx dy + c dy^2, d = centre - mean.  Over the rectangle of
-// quad offsets the minimum of q is 0 if the mean lies inside, else it is attained on an edge facing the
-// mean; along each edge q is a 1-D convex parabola (a, c > 0), minimised at the clamped vertex.
-// Rounding: the oracle's fp32 power differs from the exact one by at most ~4 ulp of
-// B = |a| X^2 + 2 |b| X Y + |c| Y^2 (X, Y the largest |offset|); q_min here carries a similar
-// error; ocml logf ~2 ulp; cugs_blend_exp_q <= 1e-6 relative.  The slack 0.01 tau + 0.05 + 4e-6 B dominates all of it
-// by orders of magnitude.  Any NaN makes the final comparison false -> not culled.
-__device__ __forceinline__ bool may_touch_quad(float4 r0, float4 r1, float qx0, float qy0,
-                                               float wx, float wy) {
-    const float mx = r0.x, my = r0.y, a = r0.z, b = r0.w, c = r1.x;
-    const float tau = r1.z;
-    if (!(tau >= 0.0f)) return false;
-    if (!(a > 0.0f && c > 0.0f)) return true;
-    const float ia = __builtin_amdgcn_rcpf(a), ic = __builtin_amdgcn_rcpf(c);   // cull only: 1 ulp is irrelevant
-    const float lx = qx0 - mx, hx = lx + wx, ly = qy0 - my, hy = ly + wy;
-    const bool inside = (lx <= 0.0f) && (hx >= 0.0f) && (ly <= 0.0f) && (hy >= 0.0f);
-    // largest |offset| per axis: lx <= hx, so max(|lx|, |hx|) = max(-lx, hx) - ONE v_max_f32 (as C, fmaxf costs two
-    // more instructions that canonicalise its inputs; the values only scale the slack)
-    float X, Y;
-    asm("v_max_f32_e64 %0, -%1, %2" : "=v"(X) : "v"(lx), "v"(hx));
-    asm("v_max_f32_e64 %0, -%1, %2" : "=v"(Y) : "v"(ly), "v"(hy));
-    const float B = a * X * X + 2.0f * fabsf(b) * X * Y + c * Y * Y;
-    const float b2 = b + b;
-    // q is convex with its minimum at the mean, so over a rectangle that does not contain the mean the minimum
-    // lies on an edge FACING the mean: the vertical edge on the mean's side if the mean is outside the x-range,
-    // the horizontal one likewise (a point of a far edge is reached from the mean through a near edge, where q
-    // is smaller).  Each at its clamped 1-D minimiser.
-    const float xe = (lx > 0.0f) ? lx : hx, ye = (ly > 0.0f) ? ly : hy;          // the near edges (if outside)
-    const float yv = __builtin_amdgcn_fmed3f(-b * xe * ic, ly, hy);             // clamp (ly <= hy): one v_med3_f32
-    const float xv = __builtin_amdgcn_fmed3f(-b * ye * ia, lx, hx);             // a NaN input still reaches q through a, b, c
-    const float qx = a * xe * xe + b2 * xe * yv + c * yv * yv;
-    const float qy = a * xv * xv + b2 * xv * ye + c * ye * ye;
-    const bool out_x = !((lx <= 0.0f) && (hx >= 0.0f)), out_y = !((ly <= 0.0f) && (hy >= 0.0f));
-    const float qmin = inside ? 0.0f : fminf(out_x ? qx : 3.0e38f, out_y ? qy : 3.0e38f);
-    return !(0.5f * qmin > tau * 1.01f + 0.05f + 4e-6f * B);
 }
 
 // Bounding box, in quad coordinates 0..7, of the lanes set in `active` (lane = y*8 + x; active != 0).

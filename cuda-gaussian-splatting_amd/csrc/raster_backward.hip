@@ -119,6 +119,7 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
     const bool inside = (px < geo.width) && (py < geo.height);
     const float pxf = (float)px + 0.5f, pyf = (float)py + 0.5f;
     const float qx0 = (float)quad_x + 0.5f, qy0 = (float)quad_y + 0.5f;
+    const float tile_cx = (float)(tile_x * CUGS_TILE + CUGS_TILE / 2), tile_cy = (float)(tile_y * CUGS_TILE + CUGS_TILE / 2);
 
     const int num_in_range = range_end - range_start;
     const int num_batches = (num_in_range + CUGS_BLOCK - 1) / CUGS_BLOCK;
@@ -188,7 +189,7 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
             head = make_float4(m.x, m.y, 0.0f, 0.0f);
         }
         const float2 mean = make_float2(head.x, head.y);
-        const float4 tail = s_rec[rec + 1];                                            // c, opacity, tau, index
+        const float4 tail = s_rec[rec + 1];                                            // c, opacity, cull limit, index
         const float dy = py2 - mean.y;
         const float dx0 = px2 - mean.x, dx1 = dx0 + 1.0f, dx2 = dx0 + 2.0f, dx3 = dx0 + 3.0f;
         float t = p01.y * dx0;
@@ -287,7 +288,7 @@ void k_raster_backward(RasterGeom geo, RasterSrc src,
         __syncthreads();
         if (s_contrib[0][0][0].x * s_contrib[1][0][0].x * s_contrib[2][0][0].x * s_contrib[3][0][0].x != 0.0f) break;
 
-        stage_record<PACKED, DEPTH>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec, depths);
+        stage_record<PACKED, DEPTH>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec, tile_cx, tile_cy, depths);
         __syncthreads();
 
         if (STATS && !wave_done) ++st_batches;
@@ -539,8 +540,11 @@ __global__ void k_dbg_blend_exp(const float* __restrict__ q, float* __restrict__
 }
 // cugsdbg_may_touch_quad: the blends' cull against their own per-pixel decisions, one case per thread.
 // in: [n][8] floats {mean x, mean y, a, b, c, opacity, quad x, quad y} (quad x, y: the quad's integer pixel origin),
-// masks [n] (the open pixels, lane = y*8 + x; non-zero).  The record is made by write_packed (tau = ln(255 o) included)
-// and read back as the blends read it.  out: hit [n] (may_touch_quad against active_rect(mask)), pass [n] (bit l: lane l
+// masks [n] (the open pixels, lane = y*8 + x; non-zero).  The record is made by write_packed (tau = ln(255 o) included),
+// staged by cugs_stage_cull for the 16-aligned tile that holds the quad's origin, and read back as the blends read it
+// (an origin that is no multiple of 8 lets the quad reach up to 4 px past that tile: the limit's B is then that much
+// short, against a slack 16 times what the roundings need).
+// out: hit [n] (may_touch_quad against active_rect(mask)), pass [n] (bit l: lane l
 // is open and pixel_alpha_raw + passes_alpha_min lets the Gaussian through there), rect [n][4] (active_rect, relative
 // to the quad's first pixel centre).
 __global__ void k_dbg_may_touch_quad(int n, const float* __restrict__ in, const unsigned long long* __restrict__ masks,
@@ -551,8 +555,11 @@ __global__ void k_dbg_may_touch_quad(int n, const float* __restrict__ in, const 
     const float* c = in + (int64_t)i * 8;
     alignas(16) float rec[CUGS_PACKED_STRIDE];
     write_packed(rec, 0, c[0], c[1], Sym2{c[2], c[3], c[4]}, 0.0f, 0.0f, 0.0f, c[5]);
-    const float4 r0 = reinterpret_cast<const float4*>(rec)[0], r1 = reinterpret_cast<const float4*>(rec)[1];
+    const float4 r0 = reinterpret_cast<const float4*>(rec)[0];
+    float4 r1 = reinterpret_cast<const float4*>(rec)[1];
     const int quad_x = (int)c[6], quad_y = (int)c[7];
+    // staged as the blends stage it, for the 16-aligned tile of the quad's origin
+    cugs_stage_cull(r0, r1, (float)((quad_x & ~(CUGS_TILE - 1)) + CUGS_TILE / 2), (float)((quad_y & ~(CUGS_TILE - 1)) + CUGS_TILE / 2));
     const float qx0 = (float)quad_x + 0.5f, qy0 = (float)quad_y + 0.5f;
     const unsigned long long active = masks[i];
     const ActiveRect ar = active_rect(active, qx0, qy0);

@@ -56,6 +56,7 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
     const bool inside = (px < geo.width) && (py < geo.height);
     const float pxf = (float)px + 0.5f, pyf = (float)py + 0.5f;
     const float qx0 = (float)quad_x + 0.5f, qy0 = (float)quad_y + 0.5f;
+    const float tile_cx = (float)(tile_x * CUGS_TILE + CUGS_TILE / 2), tile_cy = (float)(tile_y * CUGS_TILE + CUGS_TILE / 2);
 
     const int num_in_range = range_end - range_start;
     const int num_batches = (num_in_range + CUGS_BLOCK - 1) / CUGS_BLOCK;
@@ -97,7 +98,7 @@ __device__ __forceinline__ void raster_forward_tile(RasterGeom geo, RasterSrc sr
         __syncthreads();
         if (s_wave_done[0] & s_wave_done[1] & s_wave_done[2] & s_wave_done[3]) break;
 
-        stage_record<PACKED, DEPTH>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec, depths);
+        stage_record<PACKED, DEPTH>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec, tile_cx, tile_cy, depths);
         __syncthreads();
 
         if (!wave_done) {

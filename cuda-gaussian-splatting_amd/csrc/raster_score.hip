@@ -23,12 +23,13 @@
 
 namespace {
 
-// LDS record: the two geometry chunks {mx, my, a, b} {c, o, tau, g}.  The stride stays three float4s - an odd stride
+// LDS record: the two geometry chunks {mx, my, a, b} {c, o, cull limit, g}.  The stride stays three float4s - an odd stride
 // keeps the cull's one-record-per-lane 16-byte reads free of bank conflicts, as in the forward - the third is not used.
 #define CUGS_SCORE_REC_F4 3
 
 template <bool PACKED>
-__device__ __forceinline__ void stage_geometry(const RasterSrc& s, int li, int end, float4* s_rec) {
+__device__ __forceinline__ void stage_geometry(const RasterSrc& s, int li, int end, float4* s_rec, float tile_cx,
+                                               float tile_cy) {
     if (li >= end) return;
     const int g = s.gidx[li];
     float4 r0, r1;
@@ -41,6 +42,7 @@ __device__ __forceinline__ void stage_geometry(const RasterSrc& s, int li, int e
         r1 = make_float4(c, o, (o >= (1.0f / 255.0f)) ? logf(255.0f * o) : -1.0f, 0.0f);
     }
     r1.w = __int_as_float(g);
+    cugs_stage_cull(r0, r1, tile_cx, tile_cy);                     // word 6: tau -> the cull's limit for this tile
     s_rec[threadIdx.x * CUGS_SCORE_REC_F4 + 0] = r0;
     s_rec[threadIdx.x * CUGS_SCORE_REC_F4 + 1] = r1;
 }
@@ -110,6 +112,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_blend_scores(RasterGeom geo, Ras
     const bool inside = (px < geo.width) && (py < geo.height);
     const float pxf = (float)px + 0.5f, pyf = (float)py + 0.5f;
     const float qx0 = (float)quad_x + 0.5f, qy0 = (float)quad_y + 0.5f;
+    const float tile_cx = (float)(tile_x * CUGS_TILE + CUGS_TILE / 2), tile_cy = (float)(tile_y * CUGS_TILE + CUGS_TILE / 2);
 
     const int num_in_range = range_end - range_start;
     const int num_batches = (num_in_range + CUGS_BLOCK - 1) / CUGS_BLOCK;
@@ -156,7 +159,7 @@ __global__ __launch_bounds__(CUGS_BLOCK) void k_blend_scores(RasterGeom geo, Ras
         __syncthreads();
         if (s_wave_done[0] & s_wave_done[1] & s_wave_done[2] & s_wave_done[3]) break;
 
-        stage_geometry<PACKED>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec);
+        stage_geometry<PACKED>(src, range_start + batch * CUGS_BLOCK + tid, range_end, s_rec, tile_cx, tile_cy);
         __syncthreads();
 
         if (!wave_done) {
