@@ -16,26 +16,29 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional
+from typing import Dict, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import DensifyArray, check, lib
-from .rasterizer import _ptr, _stream, _torch_check
+from .rasterizer import _ptr, _skey, _stream, _torch_check
 from .types import GaussianModel
 
 K_RESET_OPACITY = -4.59511985013459           # densification.cpp:27: log(0.01 / 0.99)
 
-_workspaces = {}
+_workspaces: Dict[tuple, torch.Tensor] = {}
 
 
 def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    ws = _workspaces.get(device)
+    """Grow-only scratch per (device, stream): cugs_densify_plan leaves the prefixes cugs_densify_apply reads back, so
+    two loops on two streams of one device must not share it (importance.prune_gaussians borrows this one)."""
+    key = _skey(device)
+    ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=device)
-        _workspaces[device] = ws
+        _workspaces[key] = ws
     return ws
 
 

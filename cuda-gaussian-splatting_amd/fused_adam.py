@@ -8,6 +8,7 @@ ParamGroup, PositionLRConfig, position_lr, active_sh_degree_for_step, lr_default
 from __future__ import annotations
 
 import ctypes as C
+import ctypes.util
 import enum
 import math
 from dataclasses import dataclass, field
@@ -35,16 +36,23 @@ class PositionLRConfig:
     max_steps: int = 30000
 
 
+_libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+for _fn in (_libm.logf, _libm.expf):
+    _fn.restype, _fn.argtypes = C.c_float, [C.c_float]
+
+
 def position_lr(step: int, config: PositionLRConfig) -> float:
-    """Log-linear interpolation in float32 (lr_schedule.hpp:49-57)."""
+    """Log-linear interpolation in float32 (lr_schedule.hpp:49-57), with the C library's logf and expf as the
+    reference's std::log(float) and std::exp(float) are: numpy's vectorised float32 log and exp differ from them in
+    the last bit at some steps, and the schedule is compared for equality (tests/test_gpu_trainloop.py)."""
     f32 = np.float32
     if step >= config.max_steps:
         return float(f32(config.lr_final))
     if step <= 0:
         return float(f32(config.lr_init))
     t = f32(step) / f32(config.max_steps)
-    log_ratio = np.log(f32(config.lr_final) / f32(config.lr_init), dtype=f32)
-    return float(f32(config.lr_init) * np.exp(t * log_ratio, dtype=f32))
+    log_ratio = f32(_libm.logf(float(f32(config.lr_final) / f32(config.lr_init))))
+    return float(f32(config.lr_init) * f32(_libm.expf(float(t * log_ratio))))
 
 
 def active_sh_degree_for_step(step: int, max_degree: int) -> int:

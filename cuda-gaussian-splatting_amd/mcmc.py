@@ -24,23 +24,26 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
 from ._lib import McmcFused, check, lib
-from .rasterizer import _ptr, _stream, _torch_check
+from .rasterizer import _ptr, _skey, _stream, _torch_check
 from .types import GaussianModel
 
-_workspaces = {}
+_workspaces: Dict[tuple, torch.Tensor] = {}
 
 
 def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    ws = _workspaces.get(device)
+    """Grow-only scratch per (device, stream): the relocation's scans and the regulariser's partial sums live here from
+    one launch to the next of the same call, so two loops on two streams of one device must not share it."""
+    key = _skey(device)
+    ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=device)
-        _workspaces[device] = ws
+        _workspaces[key] = ws
     return ws
 
 

@@ -812,7 +812,9 @@ def test_fused_adam_backward_equals_backward_then_adam(pkg, dev, n, w, h, deg, s
     BIT FOR BIT over three steps (moments carried, bias corrections advancing) - same arithmetic, same order;
     only the blend backward's atomics may reorder sums, so both paths consume the SAME accumulator rows.
     With degree-3 storage both launches keep the FACTORS of the SH gradient rows in LDS; the last case
-    has fewer active coefficients than stored ones and a ragged last workgroup."""
+    has fewer active coefficients than stored ones and a ragged last workgroup.
+    After the third step both twins densify (same statistics, same noise, densify(optimizer=) on their own optimizers)
+    and run two more steps at the new N: everything stays bit for bit equal, exactly as before the event."""
     arrays, cam = _scene(pkg, n, w, h, stored, seed=n, mu_s=-3.7)
     settings = pkg.RenderSettings(background=[0.2, 0.1, 0.3], active_sh_degree=deg)
     g = torch.from_numpy(pkg.scene.make_dl_dcolor(w, h, seed=n + 1) * 3000.0).to(dev)    # gradients large enough to move parameters
@@ -820,7 +822,28 @@ def test_fused_adam_backward_equals_backward_then_adam(pkg, dev, n, w, h, deg, s
     oa, ob = pkg.FusedAdam(ma), pkg.FusedAdam(mb)
     R = pkg.rasterizer
     names = ("positions", "sh_coeffs", "opacities", "scales", "rotations")
-    for step in range(3):
+    # the hand-off to densification: after step 2 both twins accumulate their (equal) dL_dmeans_2d, densify with the same
+    # noise, each through its OWN optimizer, and go on for two more steps - the fused launch takes the moment pointers
+    # afresh each step, so the carried rows, the zeroed new rows and the running step count must serve both paths alike
+    dcfg = pkg.DensificationConfig(densify_from=0, densify_every=5, opacity_threshold=0.3, percent_dense=0.0376)
+    ca, cb = pkg.DensificationController(dcfg, 1.0), pkg.DensificationController(dcfg, 1.0)
+    for step in range(5):
+        if step == 3:
+            assert not torch.equal(ma.positions, torch.from_numpy(arrays["positions"]).to(dev))   # three steps moved the model
+            for ctrl, dm in ((ca, dm_a), (cb, dm_b)):
+                ctrl.accumulate_gradients(dm, out.radii)
+            # half of the visible rows over the threshold; by size about half of them clone and half split
+            dcfg.grad_threshold = float(dm_a.norm(2, dim=1)[out.radii > 0].median())
+            noise = torch.randn((2, n, 3), generator=torch.Generator().manual_seed(n)).to(dev)
+            sa = ca.densify(ma, 5, noise, optimizer=oa)
+            sb = cb.densify(mb, 5, noise, optimizer=ob)
+            assert sa == sb and sa.num_cloned > 0 and sa.num_split > 0 and sa.num_pruned > sa.num_split
+            n = ma.num_gaussians()
+            assert n == sa.num_after == mb.num_gaussians() and n != arrays["positions"].shape[0]
+            for i, k in enumerate(names):
+                assert torch.equal(getattr(ma, k), getattr(mb, k)), ("densify", k)
+                assert torch.equal(oa.m_[i], ob.m_[i]) and torch.equal(oa.v_[i], ob.v_[i]), ("densify", k)
+                assert oa.m_[i].shape == getattr(ma, k).shape and bool(oa.m_[i].any()) and not bool(oa.m_[i][-1].any())
         out = pkg.render(ma, cam, settings)
         assert all(torch.equal(getattr(ma, k), getattr(mb, k)) for k in names)
         rb = R.rasterize_backward(g, out.means_2d, out.cov_2d_inv, out.rgb, out.opacities_act, out.tile_ranges,
@@ -856,7 +879,7 @@ def test_fused_adam_backward_equals_backward_then_adam(pkg, dev, n, w, h, deg, s
     out = pkg.render(mb, cam, settings)
     res = pkg.render_backward(g, out, mb, cam, settings, fused_adam=ob)
     assert res.dL_dpositions is None and res.dL_dsh_coeffs is None and res.dL_dmeans_2d.shape == (n, 2)
-    assert ob.step_count_ == 4
+    assert ob.step_count_ == 6
 
 
 def test_backward_with_clamped_alphas_and_tiny_images(pkg, orc, dev):
