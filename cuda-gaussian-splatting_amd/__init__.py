@@ -32,5 +32,7 @@ from .views import StreamedViewCache, ViewCache, image_to_float, load_image_resi
 from .metrics import EvalResults, ImageMetrics, compute_psnr, compute_ssim, eval_metrics, evaluate  # noqa: F401
 from .importance import (ContributionScores, accumulate_contribution_scores, blend_scores,  # noqa: F401
                          contribution_scores, prune_by_scores, prune_gaussians)
+from .lifting import (LiftedMaps, blend_lift, error_scores, lift_maps, lift_pixel_maps,  # noqa: F401
+                      select_gaussians, vote_labels)
 from .mesh import Mesh, TSDFView, TSDFVolume, extract_mesh, write_mesh_ply  # noqa: F401
 from . import parallel, scene  # noqa: F401

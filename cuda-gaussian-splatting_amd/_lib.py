@@ -158,6 +158,7 @@ SIGNATURES = {
     "cugs_rasterize_forward_opts": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                          _P, _P, _P, C.POINTER(BlendForwardOpts), _P]),
     "cugs_blend_scores": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "cugs_blend_lift": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P]),
     "cugs_rasterize_backward": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _L, _P, _P, _P, _P, _P, _P]),
     "cugs_rasterize_backward_opts": (_I, [_I, _I, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P,

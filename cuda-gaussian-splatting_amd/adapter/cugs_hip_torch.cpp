@@ -1604,4 +1604,147 @@ int64_t prune_by_scores(ModelTensors& model, const ContributionScores& scores, f
     return prune_gaussians(model, mask, optimizer);
 }
 
+// ---- pixel maps lifted onto Gaussians ----
+LiftedMaps::LiftedMaps(int64_t n, const torch::Device& device, int channels_)
+    : table(torch::zeros({n, 4}, torch::TensorOptions().dtype(torch::kFloat32).device(device))), channels(channels_) {
+    TORCH_CHECK(channels >= 1 && channels <= 4, "LiftedMaps: channels must be 1..4");
+}
+torch::Tensor LiftedMaps::sums() const { return table.narrow(1, 0, channels); }
+void LiftedMaps::reset() { table.zero_(); num_views = 0; }
+
+namespace {
+// the validated, contiguous map of one launch: exactly one of the two comes back defined
+std::pair<torch::Tensor, torch::Tensor> lift_map_args(const LiftedMaps& lifted, int width, int height,
+                                                      const torch::Tensor& maps, const torch::Tensor& labels,
+                                                      const char* what) {
+    TORCH_CHECK(maps.defined() != labels.defined(), what, ": give exactly one of maps and labels");
+    if (maps.defined()) {
+        TORCH_CHECK(maps.device() == lifted.table.device() && maps.scalar_type() == torch::kFloat32, what,
+                    ": maps must be a float32 tensor on the table's device");
+        const bool ok = (maps.dim() == 3 && maps.size(0) == height && maps.size(1) == width && maps.size(2) == lifted.channels) ||
+                        (lifted.channels == 1 && maps.dim() == 2 && maps.size(0) == height && maps.size(1) == width);
+        TORCH_CHECK(ok, what, ": maps must be [", height, ", ", width, ", ", lifted.channels, "]");
+        return {maps.contiguous(), torch::Tensor()};
+    }
+    TORCH_CHECK(labels.device() == lifted.table.device() && labels.scalar_type() == torch::kInt32, what,
+                ": labels must be an int32 tensor on the table's device");
+    TORCH_CHECK(labels.dim() == 2 && labels.size(0) == height && labels.size(1) == width, what, ": labels must be [",
+                height, ", ", width, "]");
+    return {torch::Tensor(), labels.contiguous()};
+}
+
+void launch_lift(LiftedMaps& lifted, int width, int height, const torch::Tensor& tile_ranges,
+                 const torch::Tensor& gaussian_indices, const torch::Tensor& means_2d, const torch::Tensor& cov_2d_inv,
+                 const torch::Tensor& opacities_act, const torch::Tensor& packed, const torch::Tensor& tile_order,
+                 const torch::Tensor& maps, const torch::Tensor& labels, int label_base) {
+    auto tr = tile_ranges.contiguous(), gi = gaussian_indices.contiguous();
+    auto m = means_2d.contiguous(), c = cov_2d_inv.contiguous(), op = opacities_act.contiguous();
+    auto pk = packed.defined() ? packed.contiguous() : packed;
+    if (tile_order.defined())
+        TORCH_CHECK(tile_order.is_contiguous() && tile_order.scalar_type() == torch::kInt32 &&
+                    tile_order.numel() == 4 * tr.size(0), "tile_order must be a contiguous [tiles, 4] int32 tensor");
+    check(cugs_blend_lift(width, height, ptr<int32_t>(tr), ptr<int32_t>(gi), ptr<float>(m), ptr<float>(c), ptr<float>(op),
+                          ptr<float>(pk), order_ptr(tile_order), static_cast<int>(lifted.n()), ptr<float>(maps),
+                          ptr<int32_t>(labels), lifted.channels, label_base,
+                          lifted.n() > 0 ? lifted.table.data_ptr() : nullptr, stream_of(lifted.table)),
+          "cugs_blend_lift");
+    ++lifted.num_views;
+}
+
+// projection at SH degree 0 (the colour is not used), the plain sort (one host sync) and the lift launch
+struct SortedView { ProjectionOutput proj; SortingOutput srt; };
+SortedView sorted_view(const ModelTensors& model, const cugs_camera& cam, const RenderSettings& settings) {
+    auto proj = project_gaussians(model.positions, model.rotations, model.scales, model.opacities, model.sh_coeffs, cam,
+                                  0, settings.scale_modifier);
+    auto srt = sort_gaussians(proj.means_2d, proj.depths, proj.radii, proj.tiles_touched, cam.width, cam.height);
+    return {proj, srt};
+}
+void launch_lift_sorted(LiftedMaps& lifted, const cugs_camera& cam, const SortedView& v, const torch::Tensor& maps,
+                        const torch::Tensor& labels, int label_base) {
+    launch_lift(lifted, cam.width, cam.height, v.srt.tile_ranges, v.srt.gaussian_values_sorted, v.proj.means_2d,
+                v.proj.cov_2d_inv, v.proj.opacities_act, v.proj.packed, {}, maps, labels, label_base);
+}
+}  // namespace
+
+void lift_pixel_maps(LiftedMaps& lifted, const RenderOutput& out, const cugs_camera& camera, const torch::Tensor& maps,
+                     const torch::Tensor& labels, int label_base) {
+    const int64_t n = out.means_2d.size(0);
+    TORCH_CHECK(n == lifted.n(), "lift_pixel_maps: the table holds ", lifted.n(), " Gaussians, the render ", n);
+    auto args = lift_map_args(lifted, camera.width, camera.height, maps, labels, "lift_pixel_maps");
+    if (n == 0) { ++lifted.num_views; return; }
+    TORCH_CHECK(out.means_2d.device() == lifted.table.device(), "lift_pixel_maps: the table is on another device");
+    launch_lift(lifted, camera.width, camera.height, out.tile_ranges, out.gaussian_indices, out.means_2d, out.cov_2d_inv,
+                out.opacities_act, out.packed, out.tile_order, args.first, args.second, label_base);
+}
+
+LiftedMaps lift_maps(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                     const std::vector<torch::Tensor>& maps_per_view, const RenderSettings& settings, int channels) {
+    TORCH_CHECK(model.positions.is_cuda(), "GaussianModel must be on CUDA device");
+    TORCH_CHECK(maps_per_view.size() == cameras.size(), "lift_maps: one map per camera");
+    if (channels <= 0)
+        channels = (maps_per_view.empty() || maps_per_view[0].dim() == 2) ? 1 : static_cast<int>(maps_per_view[0].size(2));
+    const int64_t n = model.positions.size(0);
+    LiftedMaps lifted(n, model.positions.device(), channels);
+    for (size_t i = 0; i < cameras.size(); ++i) {
+        const auto& cam = cameras[i];
+        auto args = lift_map_args(lifted, cam.width, cam.height, maps_per_view[i], {}, "lift_maps");
+        if (n == 0) { ++lifted.num_views; continue; }
+        launch_lift_sorted(lifted, cam, sorted_view(model, cam, settings), args.first, {}, 0);
+    }
+    return lifted;
+}
+
+std::pair<torch::Tensor, torch::Tensor> vote_labels(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                                                    const std::vector<torch::Tensor>& label_maps, int num_labels,
+                                                    const RenderSettings& settings) {
+    TORCH_CHECK(model.positions.is_cuda(), "GaussianModel must be on CUDA device");
+    TORCH_CHECK(label_maps.size() == cameras.size(), "vote_labels: one map per camera");
+    TORCH_CHECK(num_labels >= 1, "vote_labels: num_labels must be positive");
+    const int64_t n = model.positions.size(0);
+    std::vector<LiftedMaps> windows;
+    for (int base = 0; base < num_labels; base += 4)
+        windows.emplace_back(n, model.positions.device(), std::min(4, num_labels - base));
+    for (size_t i = 0; i < cameras.size(); ++i) {
+        const auto& cam = cameras[i];
+        auto args = lift_map_args(windows[0], cam.width, cam.height, {}, label_maps[i], "vote_labels");
+        if (n == 0) continue;
+        const auto view = sorted_view(model, cam, settings);
+        for (size_t k = 0; k < windows.size(); ++k)
+            launch_lift_sorted(windows[k], cam, view, {}, args.second, static_cast<int>(4 * k));
+    }
+    std::vector<torch::Tensor> parts;
+    for (const auto& win : windows) parts.push_back(win.sums());
+    auto votes = torch::cat(parts, 1);
+    auto labels = votes.argmax(1);
+    auto top = votes.gather(1, labels.unsqueeze(1)).squeeze(1);
+    labels = torch::where(top.gt(0.0f), labels, torch::full_like(labels, -1));
+    return {labels, votes};
+}
+
+torch::Tensor error_scores(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                           const std::vector<torch::Tensor>& error_maps, const RenderSettings& settings,
+                           bool max_over_views) {
+    TORCH_CHECK(model.positions.is_cuda(), "GaussianModel must be on CUDA device");
+    TORCH_CHECK(error_maps.size() == cameras.size(), "error_scores: one map per camera");
+    const int64_t n = model.positions.size(0);
+    LiftedMaps scratch(n, model.positions.device(), 1);
+    auto out = torch::zeros({n}, fopt(model.positions));
+    for (size_t i = 0; i < cameras.size(); ++i) {
+        const auto& cam = cameras[i];
+        auto args = lift_map_args(scratch, cam.width, cam.height, error_maps[i], {}, "error_scores");
+        if (n == 0) continue;
+        if (max_over_views) scratch.reset();
+        launch_lift_sorted(scratch, cam, sorted_view(model, cam, settings), args.first, {}, 0);
+        if (max_over_views) out = torch::maximum(out, scratch.sums().select(1, 0));
+    }
+    if (!max_over_views) out.copy_(scratch.sums().select(1, 0));
+    return out;
+}
+
+int64_t select_gaussians(ModelTensors& model, const torch::Tensor& keep_mask, FusedAdam* optimizer) {
+    TORCH_CHECK(keep_mask.defined() && keep_mask.scalar_type() == torch::kBool, "select_gaussians: keep_mask must be a bool tensor");
+    prune_gaussians(model, keep_mask.logical_not(), optimizer);
+    return model.positions.size(0);
+}
+
 }  // namespace cugs_hip

@@ -405,4 +405,38 @@ int64_t prune_gaussians(ModelTensors& model, const torch::Tensor& prune_mask, Fu
 int64_t prune_by_scores(ModelTensors& model, const ContributionScores& scores, float min_max_weight = -1.0f,
                         float keep_fraction = -1.0f, FusedAdam* optimizer = nullptr);
 
+// Pixel maps lifted onto Gaussians (not in the reference): S[g,c] = sum_p w_g(p) M_c(p) with the forward's
+// blend weight w = alpha T.  The table is [N,4] float32, zeroed at construction; every launch (cugs_blend_lift) ADDS to
+// words 0..channels-1 of a row and never writes the others.
+struct LiftedMaps {
+    LiftedMaps(int64_t n, const torch::Device& device, int channels = 1);
+    torch::Tensor table;                                   // [N,4] float32
+    int channels;
+    int num_views = 0;
+    int64_t n() const { return table.size(0); }
+    torch::Tensor sums() const;                            // [N,channels] float32, a view of the table
+    void reset();
+};
+// One launch from an existing RenderOutput; needs no for_backward state.  Exactly one of `maps` ([H,W,C] float32, or
+// [H,W] for C = 1) and `labels` ([H,W] int32: channel c is the indicator of label_base + c) is defined.
+void lift_pixel_maps(LiftedMaps& lifted, const RenderOutput& render_out, const cugs_camera& camera,
+                     const torch::Tensor& maps, const torch::Tensor& labels = {}, int label_base = 0);
+// Offline, as contribution_scores: per view the projection at SH degree 0, the plain sort and the lift launch of
+// maps_per_view[i].  channels <= 0: the first map's (1 for an [H,W] map).
+LiftedMaps lift_maps(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                     const std::vector<torch::Tensor>& maps_per_view, const RenderSettings& settings = {}, int channels = 0);
+// votes[g,l] = sum over views and pixels of w_g(p) [label(p) == l] for l in 0..num_labels-1 (per view one projection and
+// sort, ceil(num_labels / 4) launches); labels[g] = the first maximum of votes[g], -1 where a Gaussian collected no vote.
+// Returns {labels [N] int64, votes [N,num_labels] float32}.
+std::pair<torch::Tensor, torch::Tensor> vote_labels(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                                                    const std::vector<torch::Tensor>& label_maps, int num_labels,
+                                                    const RenderSettings& settings = {});
+// [N] float32: per view sum_p w_g(p) err(p) of error_maps[i] ([H,W] float32), the views combined by the maximum
+// (max_over_views, the rule of "Revising Densification in Gaussian Splatting") or by addition.
+torch::Tensor error_scores(const ModelTensors& model, const std::vector<cugs_camera>& cameras,
+                           const std::vector<torch::Tensor>& error_maps, const RenderSettings& settings = {},
+                           bool max_over_views = true);
+// The complement of prune_gaussians: keeps the rows whose entry of `keep_mask` is set.  Returns the number kept.
+int64_t select_gaussians(ModelTensors& model, const torch::Tensor& keep_mask, FusedAdam* optimizer = nullptr);
+
 }  // namespace cugs_hip

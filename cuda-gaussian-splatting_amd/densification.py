@@ -122,6 +122,24 @@ class DensificationController:
         check(lib.cugs_densify_accumulate(n, _ptr(g), _ptr(r), _ptr(self.grad_accum_), _ptr(self.grad_count_),
                                           _ptr(self.max_radii_2d_), _stream(g.device)), "cugs_densify_accumulate")
 
+    def accumulate_error_scores(self, scores: torch.Tensor, radii: torch.Tensor) -> None:
+        """Error-based densification (Bulo et al., "Revising Densification in Gaussian Splatting"): `scores` [N] float32
+        is one view's per-Gaussian error E_g = sum_p w_g(p) err(p) (lifting.error_scores, or LiftedMaps.sums[:, 0] of
+        the view just rendered), `radii` [N] that view's radii.  grad_accum_ = max(grad_accum_, scores) and grad_count_
+        stays at zero, so the accum / max(count, 1) that densify() compares with config.grad_threshold is the MAXIMUM of
+        the scores over the window's views; max_radii_2d_ is updated as accumulate_gradients updates it.
+        One densification window uses either this method or accumulate_gradients, never both - they keep different
+        quantities in the same accumulator - and config.grad_threshold is then on the error scale (the error map's
+        units times pixels), not on the 2-D gradient's."""
+        _torch_check(scores.is_cuda and radii.is_cuda, "accumulate_error_scores: tensors must be on CUDA")
+        _torch_check(scores.dim() == 1, "scores must be [N]")
+        n = int(scores.shape[0])
+        _torch_check(radii.numel() == n, "radii must be [N]")
+        if self.grad_accum_ is None or self.grad_accum_.shape[0] != n or self.grad_accum_.device != scores.device:
+            self.reset_accumulators(n, scores.device)
+        torch.maximum(self.grad_accum_, scores.to(torch.float32), out=self.grad_accum_)
+        torch.maximum(self.max_radii_2d_, radii.reshape(n).to(torch.float32), out=self.max_radii_2d_)
+
     # ---- clone / split / prune ----
     def _classify(self, model: GaussianModel, step: int):
         n = model.num_gaussians()

@@ -286,6 +286,28 @@ int cugs_blend_scores(int width, int height, const int32_t* tile_ranges, const i
                       const float* means_2d, const float* cov_2d_inv, const float* opacities_act,
                       const float* packed, const void* tile_order, int n, void* scores, void* stream);
 
+/* ---- pixel maps lifted onto Gaussians (not in the reference) ----------
+ * The weighted form of cugs_blend_scores: for every Gaussian g and channel c < channels (1..4),
+ *   S[g,c] = sum over the pixels p of this view of w_g(p) * M_c(p),
+ * with the forward's decisions and the forward's w = alpha * T, bit for bit.  Exactly one of the two maps is given:
+ *   maps    [height,width,channels] float32, channel-last (the layout of the colour image); no alignment required
+ *   labels  [height,width] int32: M_c(p) = 1 where labels[p] == label_base + c, else 0 - a label outside the window
+ *           label_base .. label_base + channels - 1, negatives included, contributes nothing
+ * The sums are ADDED (float atomic adds: the last bits depend on their order) to words 0..channels-1 of row g of
+ * `table`, [n,4] float32, 16-byte aligned; words channels..3 are never written and the table is never cleared by the
+ * call: a zeroed table is the identity, V views are V calls.  A pixel's map value reaches only the Gaussians with
+ * w > 0 at that pixel - a NaN or Inf in the map goes to those rows and to no other.
+ * Other inputs as for cugs_blend_scores.  CUGS_EINVAL for a negative size, channels outside 1..4, both or neither of
+ * maps and labels when something would be launched, a NULL `table` with n > 0, gaussian_indices without a source, a
+ * NULL tile_ranges when something would be launched; then CUGS_EALIGN for packed, tile_order or table not 16-byte
+ * aligned; all before anything is queued.  n == 0 or an empty image: 0, nothing is launched.  Stream-ordered, no host
+ * sync, no workspace. */
+int cugs_blend_lift(int width, int height, const int32_t* tile_ranges, const int32_t* gaussian_indices,
+                    const float* means_2d, const float* cov_2d_inv, const float* opacities_act,
+                    const float* packed, const void* tile_order, int n,
+                    const float* maps, const int32_t* labels, int channels, int label_base,
+                    void* table, void* stream);
+
 /* ---- a7: rasterize_backward (backward.cu:239-306, kernel :31-233) -------------------
  * grad_accum: [n,CUGS_GRAD_STRIDE] floats, 64-byte aligned scratch (zeroed by the callee).  A row is
  *   {dL_drgb[3], dL_dopacity_act, M1x, M1y, M2xx, M2xy, M2yy, dL_dz, abs_x, abs_y, 0...}
