@@ -34,5 +34,7 @@ from .importance import (ContributionScores, accumulate_contribution_scores, ble
                          contribution_scores, prune_by_scores, prune_gaussians)
 from .lifting import (LiftedMaps, blend_lift, error_scores, lift_maps, lift_pixel_maps,  # noqa: F401
                       select_gaussians, vote_labels)
+from .transform import (Similarity, merge_gaussians, sh_rotation_matrices, similarity_from_cameras,  # noqa: F401
+                        transform_camera, transform_cameras, transform_gaussians)
 from .mesh import Mesh, TSDFView, TSDFVolume, extract_mesh, write_mesh_ply  # noqa: F401
 from . import parallel, scene  # noqa: F401

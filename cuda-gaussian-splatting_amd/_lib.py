@@ -114,6 +114,16 @@ class TsdfOpts(C.Structure):
     _fields_ = [("min_depth", C.c_float), ("min_alpha", C.c_float), ("max_weight", C.c_float)]
 
 
+class Similarity(C.Structure):
+    """struct CugsSimilarity."""
+    _fields_ = [("m", C.c_float * 9), ("t", C.c_float * 3), ("log_scale", C.c_float), ("q", C.c_float * 4),
+                ("d1", C.c_float * 9), ("d2", C.c_float * 25), ("d3", C.c_float * 49), ("flags", C.c_uint32)]
+
+
+SIMILARITY_ROTATION_IS_IDENTITY, SIMILARITY_SCALE_IS_ONE = 1, 2         # CUGS_SIMILARITY_*
+TRANSFORM_MAX_ZERO = 8                                                  # CUGS_TRANSFORM_MAX_ZERO
+
+
 class BilagridDims(C.Structure):
     """struct cugs_bilagrid_dims."""
     _fields_ = [("l", C.c_int32), ("gy", C.c_int32), ("gx", C.c_int32)]
@@ -215,6 +225,9 @@ SIGNATURES = {
     "cugs_mesh_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "cugs_mesh_plan": (_I, [C.POINTER(TsdfVolume), _F, _P, C.c_size_t, C.POINTER(C.c_int64), _P]),
     "cugs_mesh_emit": (_I, [C.POINTER(TsdfVolume), _P, C.c_size_t, _L, _L, _P, _P, _P, _P]),
+    "cugs_similarity_init": (_I, [C.POINTER(Similarity), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double]),
+    "cugs_transform_gaussians": (_I, [_L, _I, _P, _P, _P, _P, _P, C.POINTER(_P), C.POINTER(C.c_int), _I,
+                                      C.POINTER(Similarity), _P]),
     "cugs_device_count": (_I, [C.POINTER(C.c_int)]),
 }
 

@@ -1747,4 +1747,149 @@ int64_t select_gaussians(ModelTensors& model, const torch::Tensor& keep_mask, Fu
     return model.positions.size(0);
 }
 
+// ---- a model moved by a similarity ----
+Similarity Similarity::inverse() const {
+    Similarity o;
+    o.scale = 1.0 / scale;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) o.rotation[3 * i + j] = rotation[3 * j + i];
+    for (int i = 0; i < 3; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < 3; ++j) acc += o.rotation[3 * i + j] * translation[j];
+        o.translation[i] = -acc / scale;
+    }
+    return o;
+}
+
+Similarity Similarity::compose(const Similarity& other) const {
+    Similarity o;
+    o.scale = scale * other.scale;
+    for (int i = 0; i < 3; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < 3; ++j) {
+            double r = 0.0;
+            for (int k = 0; k < 3; ++k) r += rotation[3 * i + k] * other.rotation[3 * k + j];
+            o.rotation[3 * i + j] = r;
+            acc += rotation[3 * i + j] * other.translation[j];
+        }
+        o.translation[i] = scale * acc + translation[i];
+    }
+    return o;
+}
+
+std::array<double, 16> Similarity::matrix() const {
+    std::array<double, 16> m{};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) m[4 * i + j] = scale * rotation[3 * i + j];
+        m[4 * i + 3] = translation[i];
+    }
+    m[15] = 1.0;
+    return m;
+}
+
+bool Similarity::is_pure_translation() const {
+    for (int i = 0; i < 9; ++i)
+        if (rotation[i] != ((i % 4 == 0) ? 1.0 : 0.0)) return false;
+    return scale == 1.0;
+}
+
+CugsSimilarity Similarity::to_abi() const {
+    CugsSimilarity xf;
+    TORCH_CHECK(cugs_similarity_init(&xf, rotation.data(), translation.data(), scale) == 0,
+                "Similarity: the rotation must be a proper rotation (within 1e-4 of orthogonal, det > 0), the scale "
+                "positive and every value finite");
+    return xf;
+}
+
+void transform_gaussians(ModelTensors& model, const Similarity& sim, const torch::Tensor& mask, FusedAdam* optimizer) {
+    const int64_t n = model.positions.size(0);
+    TORCH_CHECK(model.positions.is_cuda(), "transform_gaussians: model must be on CUDA");
+    const int64_t coeffs = model.sh_coeffs.size(2);
+    TORCH_CHECK(coeffs == 1 || coeffs == 4 || coeffs == 9 || coeffs == 16, "transform_gaussians: sh_coeffs has ", coeffs,
+                " coefficients, not 1, 4, 9 or 16");
+    for (const torch::Tensor* t : {&model.positions, &model.rotations, &model.scales, &model.sh_coeffs})
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->size(0) == n,
+                    "transform_gaussians: the model's tensors must be contiguous float32 [N, ...] (the update is in place)");
+    torch::Tensor bytes;
+    if (mask.defined()) {
+        TORCH_CHECK(mask.scalar_type() == torch::kBool && mask.dim() == 1 && mask.size(0) == n,
+                    "transform_gaussians: mask must be a bool tensor of shape [", n, "]");
+        TORCH_CHECK(mask.device() == model.positions.device(), "transform_gaussians: mask must be on the model's device");
+        bytes = mask.contiguous().view(torch::kUInt8);
+    }
+    const CugsSimilarity xf = sim.to_abi();
+    std::vector<float*> zero;
+    std::vector<int> floats;
+    if (optimizer && !sim.is_pure_translation() && n > 0)
+        for (int g : {0, 1, 4})                                      // positions, SH, rotations
+            for (const torch::Tensor* t : {&optimizer->m_[g], &optimizer->v_[g]}) {
+                TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->size(0) == n,
+                            "transform_gaussians: the optimizer's moments must be contiguous float32 [N, ...]");
+                zero.push_back(t->data_ptr<float>());
+                floats.push_back(static_cast<int>(t->numel() / n));
+            }
+    if (n == 0) return;
+    check(cugs_transform_gaussians(n, static_cast<int>(coeffs), ptr<float>(model.positions), ptr<float>(model.rotations),
+                                   ptr<float>(model.scales), ptr<float>(model.sh_coeffs), ptr<uint8_t>(bytes), zero.data(),
+                                   floats.data(), static_cast<int>(zero.size()), &xf, stream_of(model.positions)),
+          "cugs_transform_gaussians");
+}
+
+cugs_camera transform_camera(const cugs_camera& camera, const Similarity& sim) {
+    cugs_camera out = camera;
+    double Rn[9], tn[3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < 3; ++k) acc += static_cast<double>(camera.view[4 * i + k]) * sim.rotation[3 * j + k];
+            Rn[3 * i + j] = acc;                                     // Rc R^T
+        }
+    for (int i = 0; i < 3; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j < 3; ++j) acc += Rn[3 * i + j] * sim.translation[j];
+        tn[i] = sim.scale * static_cast<double>(camera.view[4 * i + 3]) - acc;
+    }
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) out.view[4 * i + j] = static_cast<float>(Rn[3 * i + j]);
+        out.view[4 * i + 3] = static_cast<float>(tn[i]);
+    }
+    for (int i = 0; i < 3; ++i) {                                    // C = -R^T t of the stored float values
+        double acc = 0.0;
+        for (int j = 0; j < 3; ++j) acc += static_cast<double>(out.view[4 * j + i]) * static_cast<double>(out.view[4 * j + 3]);
+        out.cam_center[i] = static_cast<float>(-acc);
+    }
+    return out;
+}
+
+int64_t merge_gaussians(ModelTensors& model, const ModelTensors& other, FusedAdam* optimizer) {
+    torch::NoGradGuard no_grad;
+    TORCH_CHECK(other.positions.device() == model.positions.device(), "merge_gaussians: the models are on different devices");
+    const int64_t coeffs = std::max(model.sh_coeffs.size(2), other.sh_coeffs.size(2));
+    const int64_t n_new = other.positions.size(0);
+    auto pad = [&](const torch::Tensor& t) {
+        if (t.size(2) == coeffs) return t;
+        auto out = torch::zeros({t.size(0), 3, coeffs}, t.options());
+        out.slice(2, 0, t.size(2)).copy_(t);
+        return out;
+    };
+    auto join = [](const torch::Tensor& a, const torch::Tensor& b) { return torch::cat({a, b.to(a.scalar_type())}, 0).contiguous(); };
+    model.positions = join(model.positions, other.positions);
+    model.sh_coeffs = join(pad(model.sh_coeffs), pad(other.sh_coeffs));
+    model.opacities = join(model.opacities, other.opacities);
+    model.rotations = join(model.rotations, other.rotations);
+    model.scales = join(model.scales, other.scales);
+    if (optimizer) {
+        optimizer->params_ = {model.positions, model.sh_coeffs, model.opacities, model.scales, model.rotations};
+        for (int g = 0; g < 5; ++g)
+            for (auto* moments : {&optimizer->m_, &optimizer->v_}) {
+                auto old = g == 1 ? pad((*moments)[g]) : (*moments)[g];
+                auto sizes = old.sizes().vec();
+                sizes[0] = n_new;
+                (*moments)[g] = torch::cat({old, torch::zeros(sizes, old.options())}, 0).contiguous();
+            }
+        optimizer->zero_grad();
+    }
+    return model.positions.size(0);
+}
+
 }  // namespace cugs_hip

@@ -116,6 +116,7 @@ torch::Tensor evaluate_sh_backward_cuda(int degree, const torch::Tensor& sh_coef
 RenderOutput render(const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
                     bool for_backward = true, bool want_depth_map = false);
 class FusedAdam;
+struct Similarity;
 class MCMCController;
 // `fused` (optional, not in the reference; single-GPU training): the projection backward applies the optimizer step to
 // the model in place (cugs_project_backward_adam_opts) and the five parameter gradients are never materialised (undefined
@@ -257,6 +258,8 @@ private:
     friend class DensificationController;      // carries m_/v_ through clone/split/prune
     friend class MCMCController;               // zeroes the relocated rows' moments
     friend int64_t prune_gaussians(ModelTensors&, const torch::Tensor&, FusedAdam*);   // carries m_/v_ through the prune
+    friend void transform_gaussians(ModelTensors&, const Similarity&, const torch::Tensor&, FusedAdam*);   // zeroes moments
+    friend int64_t merge_gaussians(ModelTensors&, const ModelTensors&, FusedAdam*);                                // extends m_/v_
     friend bool write_gaussian_ply(const std::string&, const ModelTensors&, const FusedAdam*);
     friend ModelTensors read_gaussian_ply(const std::string&, const torch::Device&, FusedAdam*);
     void step_groups(const torch::Tensor* rows);     // rows: int32 [N] radii of the sparse step, or nullptr
@@ -438,5 +441,32 @@ torch::Tensor error_scores(const ModelTensors& model, const std::vector<cugs_cam
                            bool max_over_views = true);
 // The complement of prune_gaussians: keeps the rows whose entry of `keep_mask` is set.  Returns the number kept.
 int64_t select_gaussians(ModelTensors& model, const torch::Tensor& keep_mask, FusedAdam* optimizer = nullptr);
+
+// A model moved by a similarity x' = scale * rotation x + translation (not in the reference): fp64 host
+// values, the rotation row-major.  to_abi() is cugs_similarity_init (throws for what is no similarity).
+struct Similarity {
+    double scale = 1.0;
+    std::array<double, 9> rotation = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::array<double, 3> translation = {0, 0, 0};
+    Similarity inverse() const;
+    Similarity compose(const Similarity& other) const;     // self after other
+    std::array<double, 16> matrix() const;                 // row-major [[s R, t], [0, 1]]
+    bool is_pure_translation() const;
+    CugsSimilarity to_abi() const;
+};
+// One cugs_transform_gaussians launch on the current stream, in place (contiguous float32 tensors), no host sync:
+// positions' = s R p + t, scales' = scales + log s, rotations' = q_R (x) q, every SH band l >= 1 times D_l(R).  `mask`
+// (bool [N], optional): only the rows set are touched.  With `optimizer`: a pure translation leaves its moments alone;
+// otherwise the moments of the transformed rows of the positions, SH and rotations groups are zeroed in the same launch
+// (second moments are not covariant under a rotation - the precedent of densification's new rows and sparse Adam's
+// late-seen rows); scales and opacities keep theirs, the step count is unchanged.
+void transform_gaussians(ModelTensors& model, const Similarity& sim, const torch::Tensor& mask = {},
+                         FusedAdam* optimizer = nullptr);
+// Rc' = Rc R^T, tc' = s tc - Rc R^T t, in fp64, stored as float; the camera centre follows.
+cugs_camera transform_camera(const cugs_camera& camera, const Similarity& sim);
+// Appends the rows of `other` (in order) and replaces the model's tensors; differing SH degrees meet at the higher one,
+// zero-padded.  With `optimizer` the old rows keep their moments, the new rows start from zero, pending gradients are
+// cleared.  Returns the new N.
+int64_t merge_gaussians(ModelTensors& model, const ModelTensors& other, FusedAdam* optimizer = nullptr);
 
 }  // namespace cugs_hip

@@ -947,6 +947,52 @@ int cugs_mesh_plan(const cugs_tsdf_volume* vol, float min_weight, void* workspac
 int cugs_mesh_emit(const cugs_tsdf_volume* vol, void* workspace, size_t workspace_bytes, int64_t num_vertices,
                    int64_t num_faces, float* vertices, float* colors /* nullable */, int32_t* faces, void* stream);
 
+/* ---- similarity transform of a model (not in the reference) ---------------------------------------
+ * x' = s R x + t with R a proper rotation and s > 0.  On a Gaussian: positions' = s R p + t; scales' = scales + log s
+ * (log-scales); rotations' = q_R (x) q, the Hamilton product in wxyz order with q left raw, so |q'| = |q|; opacities
+ * unchanged; per channel and band l = 1..degree, sh[l^2 .. (l+1)^2)' = D_l(R) sh[l^2 .. (l+1)^2), the DC term unchanged.
+ * D_l is the rotation of band l in the real basis the projection evaluates (Y1 = -k y, Y2 = k z, Y3 = -k x, ...):
+ * Y_l(R d) = D_l Y_l(d), hence sum_k c'_k Y_k(R d) = sum_k c_k Y_k(d).  A camera (Rc, tc) that moves along,
+ * Rc' = Rc R^T, tc' = s tc - Rc R^T t, sees camera-space coordinates scaled by s: the same image, the depth map times s.
+ *
+ * cugs_similarity_init (host only, no device work): CUGS_EINVAL for a NULL argument, a non-finite input, scale <= 0,
+ * max |R^T R - I| > 1e-4 or det R < 0 (no reflections).  Otherwise R is first replaced by the nearest rotation, in fp64,
+ * and every field below derives from that rotation in fp64 and is rounded to fp32 once.  For a signed permutation matrix
+ * every D_l is an exact signed permutation; for the identity every matrix is exactly I and q = (1, 0, 0, 0).
+ *
+ * cugs_transform_gaussians: one launch, in place, no workspace, no host sync.  positions [n,3], rotations [n,4],
+ * scales [n,3], sh [n,3,sh_coeffs] with sh_coeffs in {1, 4, 9, 16}; pointers need dword alignment only (16-byte accesses
+ * are used where the pointer and sh_coeffs allow them: the same bits either way).  `mask` (n bytes, nullable): a row
+ * whose byte is 0 is neither read nor written.  zero_rows_host / zero_row_floats_host: HOST arrays of num_zero
+ * (0..CUGS_TRANSFORM_MAX_ZERO) DEVICE arrays [n, zero_row_floats[k]] whose rows are set to 0.0f for exactly the rows
+ * transformed (an optimizer's moments).  Arithmetic, each product and each sum rounded to fp32 on its own:
+ *   positions   acc = m[3i] x; acc = acc + m[3i+1] y; acc = acc + m[3i+2] z; out_i = acc + t[i]
+ *   scales      out = scale + log_scale                         (skipped with CUGS_SIMILARITY_SCALE_IS_ONE: bits kept)
+ *   rotations   a = q_R, b = q:  w' = aw bw - ax bx - ay by - az bz;  x' = aw bx + ax bw + ay bz - az by;
+ *               y' = aw by - ax bz + ay bw + az bx;  z' = aw bz + ax by - ay bx + az bw, each summed left to right
+ *   sh          out_i = D[i][0] c_0, then + D[i][j] c_j for j ascending
+ * With CUGS_SIMILARITY_ROTATION_IS_IDENTITY rotations and sh are not touched; with both flags and t = 0 nothing but the
+ * zero_rows is.  Checks, before anything is queued, in this order: CUGS_EINVAL for n < 0, another sh_coeffs, a NULL xf,
+ * num_zero out of range or without its arrays, a non-positive zero_row_floats, a NULL tensor or zero row array with n > 0;
+ * CUGS_EALIGN for a pointer that is not dword aligned; n = 0 then succeeds with nothing queued. */
+#define CUGS_SIMILARITY_ROTATION_IS_IDENTITY 1u
+#define CUGS_SIMILARITY_SCALE_IS_ONE 2u
+#define CUGS_TRANSFORM_MAX_ZERO 8
+typedef struct CugsSimilarity {
+    float    m[9];          /* s R, row-major */
+    float    t[3];
+    float    log_scale;     /* log s */
+    float    q[4];          /* unit quaternion of R, wxyz, w >= 0 */
+    float    d1[9];         /* D_1, row-major */
+    float    d2[25];        /* D_2 */
+    float    d3[49];        /* D_3 */
+    uint32_t flags;         /* CUGS_SIMILARITY_* */
+} CugsSimilarity;
+int cugs_similarity_init(CugsSimilarity* out, const double rotation[9], const double translation[3], double scale);
+int cugs_transform_gaussians(int64_t n, int sh_coeffs, float* positions, float* rotations, float* scales, float* sh,
+                             const uint8_t* mask /* nullable */, float* const* zero_rows_host,
+                             const int* zero_row_floats_host, int num_zero, const CugsSimilarity* xf_host, void* stream);
+
 /* Device properties the host side needs without linking the HIP runtime itself. */
 int cugs_device_count(int* count_host);
 
