@@ -7,21 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "cugs_hip_torch.hpp"
-
-static torch::Tensor load(const std::string& p, std::vector<int64_t> shape) {
-    auto t = torch::empty(shape, torch::kFloat32);
-    FILE* f = fopen(p.c_str(), "rb");
-    if (!f || fread(t.data_ptr<float>(), sizeof(float), t.numel(), f) != static_cast<size_t>(t.numel())) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    fclose(f);
-    return t.to(torch::kCUDA);
-}
-static void save(const std::string& p, const torch::Tensor& t) {
-    auto c = t.to(torch::kCPU).contiguous();
-    FILE* f = fopen(p.c_str(), "wb");
-    fwrite(c.data_ptr(), c.element_size(), c.numel(), f);
-    fclose(f);
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     setvbuf(stdout, nullptr, _IOLBF, 0);
@@ -29,12 +15,13 @@ int main(int argc, char** argv) {
     const std::string d = argv[1];
     const int64_t n = atoll(argv[2]), C = atoll(argv[3]);
     const int w = atoi(argv[4]), h = atoi(argv[5]);
+    auto load = [](const std::string& p, std::vector<int64_t> shape) { return load_tensor(p, shape, torch::kFloat32, torch::kCUDA); };
     try {
         fprintf(stderr, "[driver] start\n");
         cugs_hip::ModelTensors m{load(d + "/positions.bin", {n, 3}), load(d + "/sh_coeffs.bin", {n, 3, C}),
                                  load(d + "/opacities.bin", {n, 1}), load(d + "/rotations.bin", {n, 4}),
                                  load(d + "/scales.bin", {n, 3})};
-        auto camt = load(d + "/camera.bin", {26}).to(torch::kCPU);
+        auto camt = load_tensor(d + "/camera.bin", {26});
         const float* cf = camt.data_ptr<float>();
         cugs_camera cam{};
         for (int i = 0; i < 16; ++i) cam.view[i] = cf[i];
@@ -89,14 +76,14 @@ int main(int argc, char** argv) {
         }
         // N1 through the C++ host: loss + dL/dcolor of the render against the flipped image as a target
         auto lg = cugs_hip::combined_loss_and_grad(out.color, out.color.flip(0).contiguous());
-        save(d + "/out_loss.bin", lg.loss.reshape({1}));
-        save(d + "/out_loss_grad.bin", lg.dL_dcolor);
-        save(d + "/out_color.bin", out.color);
-        save(d + "/out_n_contrib.bin", out.n_contrib);
-        save(d + "/out_indices.bin", out.gaussian_indices);
-        save(d + "/out_dpos.bin", grads.dL_dpositions);
-        save(d + "/out_dsh.bin", grads.dL_dsh_coeffs);
-        save(d + "/out_positions_after_adam.bin", m.positions);
+        write_raw(d + "/out_loss.bin", lg.loss.reshape({1}));
+        write_raw(d + "/out_loss_grad.bin", lg.dL_dcolor);
+        write_raw(d + "/out_color.bin", out.color);
+        write_raw(d + "/out_n_contrib.bin", out.n_contrib);
+        write_raw(d + "/out_indices.bin", out.gaussian_indices);
+        write_raw(d + "/out_dpos.bin", grads.dL_dpositions);
+        write_raw(d + "/out_dsh.bin", grads.dL_dsh_coeffs);
+        write_raw(d + "/out_positions_after_adam.bin", m.positions);
         // N2 through the C++ host: statistics from this view, then one clone/split/prune cycle with the
         // moments carried over; the noise comes from the test so the Python host can reproduce the result
         {
@@ -106,9 +93,9 @@ int main(int argc, char** argv) {
             ctrl.accumulate_gradients(grads.dL_dmeans_2d, out.radii);
             auto noise = load(d + "/split_noise.bin", {2, n, 3});
             auto stats = ctrl.densify(m, 5, noise, &opt);
-            save(d + "/out_densify_positions.bin", m.positions);
-            save(d + "/out_densify_sh.bin", m.sh_coeffs);
-            save(d + "/out_densify_scales.bin", m.scales);
+            write_raw(d + "/out_densify_positions.bin", m.positions);
+            write_raw(d + "/out_densify_sh.bin", m.sh_coeffs);
+            write_raw(d + "/out_densify_scales.bin", m.scales);
             printf("densify before=%d cloned=%d split=%d pruned=%d after=%d\n", stats.num_before, stats.num_cloned,
                    stats.num_split, stats.num_pruned, stats.num_after);
             opt.apply_gradients(cugs_hip::render_backward(g, cugs_hip::render(m, cam, st), m, cam, st));
@@ -117,8 +104,8 @@ int main(int argc, char** argv) {
         // N4 through the C++ host: the 8-bit copy of the render, half-size float target
         {
             auto u8 = (out.color.clamp(0, 1) * 255.0f).to(torch::kUInt8).contiguous();
-            save(d + "/out_view_u8.bin", u8);
-            save(d + "/out_target_half.bin", cugs_hip::image_to_float(u8, w / 2, h / 2));
+            write_raw(d + "/out_view_u8.bin", u8);
+            write_raw(d + "/out_target_half.bin", cugs_hip::image_to_float(u8, w / 2, h / 2));
         }
         // N3 through the C++ host: checkpoint with optimizer state, read it back, compare
         {

@@ -7,28 +7,7 @@
 // Writes, per case, out_<i>_x.f32 ([h,w,3], corrected), out_<i>_dc.f32 ([h,w,3], dL_drendered), out_<i>_dg.f32
 // ([12,l,gy,gx], dL_dgrid of the slice), out_<i>_tv.f32 ({tv}) and out_<i>_dgtv.f32 (dL_dgrid after bilagrid_tv added
 // tv_weight * dtv/dgrid to a copy of it).
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path, size_t count) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    if (v.size() != count) { std::fprintf(stderr, "%s: %zu elements, expected %zu\n", path.c_str(), v.size(), count); std::exit(2); }
-    return v;
-}
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto host = t.contiguous().cpu();
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(host.data_ptr<float>()), host.numel() * sizeof(float));
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
@@ -40,10 +19,7 @@ int main(int argc, char** argv) {
         int ncases = 0;
         if (!(mf >> word >> ncases) || word != "cases") { std::fprintf(stderr, "bad manifest\n"); return 2; }
         auto load = [&](const std::string& name, std::vector<int64_t> shape) {
-            size_t count = 1;
-            for (auto s : shape) count *= static_cast<size_t>(s);
-            auto v = read_f32(dir + "/" + name, count);
-            return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+            return load_tensor(dir + "/" + name, shape, torch::kFloat32, dev);
         };
         for (int i = 0; i < ncases; ++i) {
             int h = 0, w = 0, l = 0, gy = 0, gx = 0;
@@ -56,11 +32,11 @@ int main(int argc, char** argv) {
             const auto back = cugs_hip::bilagrid_slice_backward(grid, c, g);
             const auto tv = cugs_hip::bilagrid_tv(grid, tv_weight, back.dL_dgrid.clone());
             const std::string out = dir + "/out_" + std::to_string(i);
-            write_f32(out + "_x.f32", x);
-            write_f32(out + "_dc.f32", back.dL_drendered);
-            write_f32(out + "_dg.f32", back.dL_dgrid);
-            write_f32(out + "_tv.f32", tv.tv.reshape({1}));
-            write_f32(out + "_dgtv.f32", tv.dL_dgrid);
+            write_raw(out + "_x.f32", x);
+            write_raw(out + "_dc.f32", back.dL_drendered);
+            write_raw(out + "_dg.f32", back.dL_dgrid);
+            write_raw(out + "_tv.f32", tv.tv.reshape({1}));
+            write_raw(out + "_dgtv.f32", tv.dL_dgrid);
         }
         bool threw = false;                                       // an [11, ...] grid is a c10::Error
         if (ncases > 0) {

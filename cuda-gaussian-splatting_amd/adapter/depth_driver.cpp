@@ -4,45 +4,18 @@
 // camera file holds the cugs_camera words: view[16] fx fy cx cy width height cam_center[3]), renders with
 // want_depth_map = true and runs render_backward with the three map gradients, and writes
 // <dir>/{depth_map,alpha,d_positions,d_rotations,d_scales,d_opacities,d_sh}.f32.
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    return v;
-}
-
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto c = t.detach().to(torch::kCPU).contiguous().to(torch::kFloat32);
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(c.data_ptr<float>()), c.numel() * sizeof(float));
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
     const std::string dir = argv[1];
     const auto dev = torch::Device(torch::kCUDA, 0);
     auto load = [&](const char* name, std::vector<int64_t> shape) {
-        auto v = read_f32(dir + "/" + name + ".f32");
-        return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+        return load_tensor(dir + "/" + name + ".f32", shape, torch::kFloat32, dev);
     };
-    const auto cam_words = read_f32(dir + "/camera.f32");
-    cugs_camera cam{};
-    for (int i = 0; i < 16; ++i) cam.view[i] = cam_words[i];
-    cam.fx = cam_words[16]; cam.fy = cam_words[17]; cam.cx = cam_words[18]; cam.cy = cam_words[19];
-    cam.width = static_cast<int>(cam_words[20]); cam.height = static_cast<int>(cam_words[21]);
-    for (int i = 0; i < 3; ++i) cam.cam_center[i] = cam_words[22 + i];
-    const int64_t n = static_cast<int64_t>(read_f32(dir + "/opacities.f32").size());
-    const int64_t c = static_cast<int64_t>(read_f32(dir + "/sh.f32").size()) / (3 * n);
+    const cugs_camera cam = read_camera(dir + "/camera.f32");
+    const int64_t n = static_cast<int64_t>(read_raw<float>(dir + "/opacities.f32").size());
+    const int64_t c = static_cast<int64_t>(read_raw<float>(dir + "/sh.f32").size()) / (3 * n);
     const int w = cam.width, h = cam.height;
     cugs_hip::ModelTensors model{load("positions", {n, 3}), load("sh", {n, 3, c}), load("opacities", {n, 1}),
                                  load("rotations", {n, 4}), load("scales", {n, 3})};
@@ -52,13 +25,13 @@ int main(int argc, char** argv) {
     auto grads = cugs_hip::render_backward(load("dl_dcolor", {h, w, 3}), out, model, cam, settings, nullptr, nullptr, 0,
                                            load("dl_ddepth", {h, w}), load("dl_dalpha", {h, w}));
     torch::cuda::synchronize();
-    write_f32(dir + "/depth_map.f32", out.depth_map);
-    write_f32(dir + "/alpha.f32", 1.0 - out.final_T);
-    write_f32(dir + "/d_positions.f32", grads.dL_dpositions);
-    write_f32(dir + "/d_rotations.f32", grads.dL_drotations);
-    write_f32(dir + "/d_scales.f32", grads.dL_dscales);
-    write_f32(dir + "/d_opacities.f32", grads.dL_dopacities);
-    write_f32(dir + "/d_sh.f32", grads.dL_dsh_coeffs);
+    write_as_f32(dir + "/depth_map.f32", out.depth_map);
+    write_as_f32(dir + "/alpha.f32", 1.0 - out.final_T);
+    write_as_f32(dir + "/d_positions.f32", grads.dL_dpositions);
+    write_as_f32(dir + "/d_rotations.f32", grads.dL_drotations);
+    write_as_f32(dir + "/d_scales.f32", grads.dL_dscales);
+    write_as_f32(dir + "/d_opacities.f32", grads.dL_dopacities);
+    write_as_f32(dir + "/d_sh.f32", grads.dL_dsh_coeffs);
     std::printf("depth_driver ok: n %lld, %dx%d\n", static_cast<long long>(n), w, h);
     return 0;
 }

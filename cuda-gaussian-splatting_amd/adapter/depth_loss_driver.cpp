@@ -7,28 +7,7 @@
 //                                                            weight)
 // Writes, per case, out_<i>_out.f32 ({loss, s, b, valid weight, valid count, fit_ok}), out_<i>_gd.f32, out_<i>_ga.f32
 // and out_<i>_x.f32 ([h,w]: dL_ddepth_map, dL_dalpha, expected) from depth_loss with the weight and a fitted alignment.
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path, size_t count) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    if (v.size() != count) { std::fprintf(stderr, "%s: %zu elements, expected %zu\n", path.c_str(), v.size(), count); std::exit(2); }
-    return v;
-}
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto host = t.contiguous().cpu();
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(host.data_ptr<float>()), host.numel() * sizeof(float));
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
@@ -40,8 +19,7 @@ int main(int argc, char** argv) {
         int ncases = 0;
         if (!(mf >> word >> ncases) || word != "cases") { std::fprintf(stderr, "bad manifest\n"); return 2; }
         auto load = [&](const std::string& name, int h, int w) {
-            auto v = read_f32(dir + "/" + name, static_cast<size_t>(h) * static_cast<size_t>(w));
-            return torch::from_blob(v.data(), {h, w}, torch::kFloat32).clone().to(dev);
+            return load_tensor(dir + "/" + name, {h, w}, torch::kFloat32, dev);
         };
         for (int i = 0; i < ncases; ++i) {
             int h = 0, w = 0, inverse = 0;
@@ -51,11 +29,11 @@ int main(int argc, char** argv) {
             auto wt = load(stem + "_w.f32", h, w);
             const auto r = cugs_hip::depth_loss(d, a, t, wt, inverse != 0, {}, true, 1e-3f, true, true);
             const std::string out = dir + "/out_" + std::to_string(i);
-            write_f32(out + "_out.f32", torch::cat({r.loss.reshape({1}), r.scale_shift, r.valid_weight.reshape({1}),
+            write_raw(out + "_out.f32", torch::cat({r.loss.reshape({1}), r.scale_shift, r.valid_weight.reshape({1}),
                                                     r.valid_count.reshape({1}), r.fit_ok.reshape({1})}));
-            write_f32(out + "_gd.f32", r.dL_ddepth_map);
-            write_f32(out + "_ga.f32", r.dL_dalpha);
-            write_f32(out + "_x.f32", r.expected);
+            write_raw(out + "_gd.f32", r.dL_ddepth_map);
+            write_raw(out + "_ga.f32", r.dL_dalpha);
+            write_raw(out + "_x.f32", r.expected);
         }
         bool threw = false;                                       // a fit together with a given (s, b) is a c10::Error
         if (ncases > 0) {

@@ -7,28 +7,7 @@
 //                                                                    is 1, case_<i>_m.f32 (float32 [h,w])
 // Writes, per case, out_<i>_loss.f32 ({loss, L1, mean SSIM}), out_<i>_dc.f32 ([h,w,3]), out_<i>_de.f32 ([3,4]) and
 // out_<i>_x.f32 ([h,w,3], the corrected image) from combined_loss_exposure.
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path, size_t count) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    if (v.size() != count) { std::fprintf(stderr, "%s: %zu elements, expected %zu\n", path.c_str(), v.size(), count); std::exit(2); }
-    return v;
-}
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto host = t.contiguous().cpu();
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(host.data_ptr<float>()), host.numel() * sizeof(float));
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
@@ -40,10 +19,7 @@ int main(int argc, char** argv) {
         int ncases = 0;
         if (!(mf >> word >> ncases) || word != "cases") { std::fprintf(stderr, "bad manifest\n"); return 2; }
         auto load = [&](const std::string& name, std::vector<int64_t> shape) {
-            size_t count = 1;
-            for (auto s : shape) count *= static_cast<size_t>(s);
-            auto v = read_f32(dir + "/" + name, count);
-            return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+            return load_tensor(dir + "/" + name, shape, torch::kFloat32, dev);
         };
         for (int i = 0; i < ncases; ++i) {
             int h = 0, w = 0, masked = 0;
@@ -55,10 +31,10 @@ int main(int argc, char** argv) {
             if (masked) m = load(stem + "_m.f32", {h, w});
             const auto r = cugs_hip::combined_loss_exposure(c, t, lambda, e, m, true, true);
             const std::string out = dir + "/out_" + std::to_string(i);
-            write_f32(out + "_loss.f32", torch::stack({r.loss, r.l1, r.ssim_mean}));
-            write_f32(out + "_dc.f32", r.dL_dcolor);
-            write_f32(out + "_de.f32", r.dL_dexposure);
-            write_f32(out + "_x.f32", r.corrected);
+            write_raw(out + "_loss.f32", torch::stack({r.loss, r.l1, r.ssim_mean}));
+            write_raw(out + "_dc.f32", r.dL_dcolor);
+            write_raw(out + "_de.f32", r.dL_dexposure);
+            write_raw(out + "_x.f32", r.corrected);
         }
         bool threw = false;                                       // a [4,3] exposure is a c10::Error
         if (ncases > 0) {

@@ -6,22 +6,7 @@
 #include <string>
 #include <vector>
 
-#include "cugs_hip_torch.hpp"
-
-static torch::Tensor load(const std::string& p, std::vector<int64_t> shape, torch::ScalarType type) {
-    auto t = torch::empty(shape, type);
-    FILE* f = fopen(p.c_str(), "rb");
-    const size_t bytes = static_cast<size_t>(t.numel()) * t.element_size();
-    if (!f || fread(t.data_ptr(), 1, bytes, f) != bytes) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    fclose(f);
-    return t;
-}
-static void save(const std::string& p, const torch::Tensor& t) {
-    auto c = t.to(torch::kCPU).contiguous();
-    FILE* f = fopen(p.c_str(), "wb");
-    fwrite(c.data_ptr(), c.element_size(), c.numel(), f);
-    fclose(f);
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     setvbuf(stdout, nullptr, _IOLBF, 0);
@@ -30,16 +15,16 @@ int main(int argc, char** argv) {
     const int64_t n = atoll(argv[2]);
     const int degree = atoi(argv[3]), k = atoi(argv[4]), route = atoi(argv[5]);
     try {
-        auto pos = load(d + "/positions.bin", {n, 3}, torch::kFloat32);          // host tensors: the layer moves them
-        auto col = load(d + "/colors.bin", {n, 3}, torch::kUInt8);
+        auto pos = load_tensor(d + "/positions.bin", {n, 3});                      // host tensors: the layer moves them
+        auto col = load_tensor(d + "/colors.bin", {n, 3}, torch::kUInt8);
         auto m = cugs_hip::init_gaussians_from_sparse(pos, col, degree, k, route);
         auto mean = cugs_hip::knn_mean_distances(pos.to(torch::kCUDA), k, route);
-        save(d + "/out_mean_dist.bin", mean);
-        save(d + "/out_positions.bin", m.positions);
-        save(d + "/out_sh_coeffs.bin", m.sh_coeffs);
-        save(d + "/out_opacities.bin", m.opacities);
-        save(d + "/out_rotations.bin", m.rotations);
-        save(d + "/out_scales.bin", m.scales);
+        write_raw(d + "/out_mean_dist.bin", mean);
+        write_raw(d + "/out_positions.bin", m.positions);
+        write_raw(d + "/out_sh_coeffs.bin", m.sh_coeffs);
+        write_raw(d + "/out_opacities.bin", m.opacities);
+        write_raw(d + "/out_rotations.bin", m.rotations);
+        write_raw(d + "/out_scales.bin", m.scales);
         bool threw = false;                                                       // gaussian_init.cpp:77-78
         try { cugs_hip::init_gaussians_from_sparse(pos, col, 4, k, route); }
         catch (const c10::Error&) { threw = true; }

@@ -11,39 +11,7 @@
 //   kept                the return of select_gaussians(labels == keep_label) with a FusedAdam that has taken one step at
 //                       learning rate 0 (moments set, parameters untouched)
 //   p_{positions,sh,opacities,rotations,scales}, m_0..m_4, v_0..v_4   the selected model and moments (group order)
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    return v;
-}
-
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto c = t.detach().to(torch::kCPU).contiguous().to(torch::kFloat32);
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(c.data_ptr<float>()), c.numel() * sizeof(float));
-}
-
-static cugs_camera read_camera(const std::string& path) {
-    const auto words = read_f32(path);
-    cugs_camera cam{};
-    for (int i = 0; i < 16; ++i) cam.view[i] = words[i];
-    cam.fx = words[16]; cam.fy = words[17]; cam.cx = words[18]; cam.cy = words[19];
-    cam.width = static_cast<int>(words[20]); cam.height = static_cast<int>(words[21]);
-    for (int i = 0; i < 3; ++i) cam.cam_center[i] = words[22 + i];
-    return cam;
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 4) { std::fprintf(stderr, "usage: %s <dir> <num_labels> <keep_label>\n", argv[0]); return 2; }
@@ -51,12 +19,11 @@ int main(int argc, char** argv) {
     const int num_labels = std::atoi(argv[2]), keep_label = std::atoi(argv[3]);
     const auto dev = torch::Device(torch::kCUDA, 0);
     auto load = [&](const std::string& name, std::vector<int64_t> shape) {
-        auto v = read_f32(dir + "/" + name + ".f32");
-        return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+        return load_tensor(dir + "/" + name + ".f32", shape, torch::kFloat32, dev);
     };
     const std::vector<cugs_camera> cams{read_camera(dir + "/camera0.f32"), read_camera(dir + "/camera1.f32")};
-    const int64_t n = static_cast<int64_t>(read_f32(dir + "/opacities.f32").size());
-    const int64_t c = static_cast<int64_t>(read_f32(dir + "/sh.f32").size()) / (3 * n);
+    const int64_t n = static_cast<int64_t>(read_raw<float>(dir + "/opacities.f32").size());
+    const int64_t c = static_cast<int64_t>(read_raw<float>(dir + "/sh.f32").size()) / (3 * n);
     const int w = cams[0].width, h = cams[0].height;
     cugs_hip::ModelTensors model{load("positions", {n, 3}), load("sh", {n, 3, c}), load("opacities", {n, 1}),
                                  load("rotations", {n, 4}), load("scales", {n, 3})};
@@ -72,18 +39,18 @@ int main(int argc, char** argv) {
     auto b = cugs_hip::lift_maps(model, cams, maps, settings);
     if (a.num_views != 2 || b.num_views != 2 || b.channels != 4) { std::fprintf(stderr, "num_views is not 2\n"); return 1; }
     if (a.sums().data_ptr() != a.table.data_ptr()) { std::fprintf(stderr, "sums() is not a view of the table\n"); return 1; }
-    write_f32(dir + "/a_sums.f32", a.sums());
-    write_f32(dir + "/b_sums.f32", b.sums());
+    write_as_f32(dir + "/a_sums.f32", a.sums());
+    write_as_f32(dir + "/b_sums.f32", b.sums());
     cugs_hip::LiftedMaps cl(n, dev, 2);
     cugs_hip::lift_pixel_maps(cl, cugs_hip::render(model, cams[0], settings, /*for_backward=*/false), cams[0], {}, labels_2d, 1);
     if (cl.table.narrow(1, 2, 2).any().item<bool>()) { std::fprintf(stderr, "words 2..3 were written\n"); return 1; }
-    write_f32(dir + "/c_sums.f32", cl.sums());
+    write_as_f32(dir + "/c_sums.f32", cl.sums());
 
     auto voted = cugs_hip::vote_labels(model, cams, {labels_2d, labels_2d}, num_labels, settings);
-    write_f32(dir + "/labels.out.f32", voted.first);
-    write_f32(dir + "/votes.f32", voted.second);
-    write_f32(dir + "/err_max.f32", cugs_hip::error_scores(model, cams, errs, settings));
-    write_f32(dir + "/err_sum.f32", cugs_hip::error_scores(model, cams, errs, settings, /*max_over_views=*/false));
+    write_as_f32(dir + "/labels.out.f32", voted.first);
+    write_as_f32(dir + "/votes.f32", voted.second);
+    write_as_f32(dir + "/err_max.f32", cugs_hip::error_scores(model, cams, errs, settings));
+    write_as_f32(dir + "/err_sum.f32", cugs_hip::error_scores(model, cams, errs, settings, /*max_over_views=*/false));
 
     // one optimizer step at learning rate 0: the moments are those of a real step, the parameters stay as voted on
     cugs_hip::FusedAdam opt({model.positions, model.sh_coeffs, model.opacities, model.scales, model.rotations},
@@ -99,15 +66,15 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "the selected model and optimizer disagree\n");
         return 1;
     }
-    write_f32(dir + "/kept.f32", torch::full({1}, static_cast<double>(kept)));
-    write_f32(dir + "/p_positions.f32", model.positions);
-    write_f32(dir + "/p_sh.f32", model.sh_coeffs);
-    write_f32(dir + "/p_opacities.f32", model.opacities);
-    write_f32(dir + "/p_rotations.f32", model.rotations);
-    write_f32(dir + "/p_scales.f32", model.scales);
+    write_as_f32(dir + "/kept.f32", torch::full({1}, static_cast<double>(kept)));
+    write_as_f32(dir + "/p_positions.f32", model.positions);
+    write_as_f32(dir + "/p_sh.f32", model.sh_coeffs);
+    write_as_f32(dir + "/p_opacities.f32", model.opacities);
+    write_as_f32(dir + "/p_rotations.f32", model.rotations);
+    write_as_f32(dir + "/p_scales.f32", model.scales);
     for (int g = 0; g < 5; ++g) {
-        write_f32(dir + "/m_" + std::to_string(g) + ".f32", opt.exp_avg()[g]);
-        write_f32(dir + "/v_" + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
+        write_as_f32(dir + "/m_" + std::to_string(g) + ".f32", opt.exp_avg()[g]);
+        write_as_f32(dir + "/v_" + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
     }
     std::printf("lift_driver ok: n %lld, %dx%d, %d labels, kept %lld\n", static_cast<long long>(n), w, h, num_labels,
                 static_cast<long long>(kept));

@@ -9,21 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "cugs_hip_torch.hpp"
-
-static torch::Tensor load(const std::string& p, std::vector<int64_t> shape) {
-    auto t = torch::empty(shape, torch::kFloat32);
-    FILE* f = fopen(p.c_str(), "rb");
-    if (!f || fread(t.data_ptr<float>(), sizeof(float), t.numel(), f) != static_cast<size_t>(t.numel())) { fprintf(stderr, "cannot read %s\n", p.c_str()); exit(2); }
-    fclose(f);
-    return t.to(torch::kCUDA);
-}
-static void save(const std::string& p, const torch::Tensor& t) {
-    auto c = t.to(torch::kCPU).contiguous();
-    FILE* f = fopen(p.c_str(), "wb");
-    fwrite(c.data_ptr(), c.element_size(), c.numel(), f);
-    fclose(f);
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     setvbuf(stdout, nullptr, _IOLBF, 0);
@@ -31,6 +17,7 @@ int main(int argc, char** argv) {
     const std::string d = argv[1];
     const int64_t n = atoll(argv[2]), C = atoll(argv[3]);
     const int w = atoi(argv[4]), h = atoi(argv[5]);
+    auto load = [](const std::string& p, std::vector<int64_t> shape) { return load_tensor(p, shape, torch::kFloat32, torch::kCUDA); };
     try {
         cugs_hip::ModelTensors m{load(d + "/positions.bin", {n, 3}), load(d + "/sh_coeffs.bin", {n, 3, C}),
                                  load(d + "/opacities.bin", {n, 1}), load(d + "/rotations.bin", {n, 4}),
@@ -57,17 +44,17 @@ int main(int argc, char** argv) {
         opt.step();
         ctrl.inject_noise(m, 3);
         const auto st = ctrl.relocate(m, 3, &opt);
-        save(d + "/out_value.bin", value.reshape({1}));
-        save(d + "/out_positions.bin", m.positions);
-        save(d + "/out_sh_coeffs.bin", m.sh_coeffs);
-        save(d + "/out_opacities.bin", m.opacities);
-        save(d + "/out_rotations.bin", m.rotations);
-        save(d + "/out_scales.bin", m.scales);
+        write_raw(d + "/out_value.bin", value.reshape({1}));
+        write_raw(d + "/out_positions.bin", m.positions);
+        write_raw(d + "/out_sh_coeffs.bin", m.sh_coeffs);
+        write_raw(d + "/out_opacities.bin", m.opacities);
+        write_raw(d + "/out_rotations.bin", m.rotations);
+        write_raw(d + "/out_scales.bin", m.scales);
         printf("relocate dead=%d moved=%d total=%d should=%d,%d\n", st.num_dead, st.num_relocated, st.num_total,
                ctrl.should_relocate(500) ? 1 : 0, ctrl.should_relocate(501) ? 1 : 0);
 
         // (2) the fused route through render_backward
-        auto camt = load(d + "/camera.bin", {26}).to(torch::kCPU);
+        auto camt = load_tensor(d + "/camera.bin", {26});
         const float* cf = camt.data_ptr<float>();
         cugs_camera cam{};
         for (int i = 0; i < 16; ++i) cam.view[i] = cf[i];
@@ -80,9 +67,9 @@ int main(int argc, char** argv) {
         cugs_hip::FusedAdam opt2({m2.positions, m2.sh_coeffs, m2.opacities, m2.scales, m2.rotations}, lrs);
         auto out = cugs_hip::render(m2, cam, rs);
         auto res = cugs_hip::render_backward(dl, out, m2, cam, rs, &opt2, &ctrl, 3);
-        save(d + "/out_fused_positions.bin", m2.positions);
-        save(d + "/out_fused_opacities.bin", m2.opacities);
-        save(d + "/out_fused_scales.bin", m2.scales);
+        write_raw(d + "/out_fused_positions.bin", m2.positions);
+        write_raw(d + "/out_fused_opacities.bin", m2.opacities);
+        write_raw(d + "/out_fused_scales.bin", m2.scales);
         bool threw = false;                            // the MCMC route without the fused optimizer step is refused
         try { cugs_hip::render_backward(dl, cugs_hip::render(m2, cam, rs), m2, cam, rs, nullptr, &ctrl, 4); }
         catch (const c10::Error&) { threw = true; }

@@ -9,28 +9,7 @@
 //                                           [h,w,3], with colour), view_<i>_w.f32 (float32 [h,w], with has_weight)
 // Fuses the views in one tsdf_integrate call (batches of 16 inside) and extracts.  Writes out_planes.f32 ([P,nz,ny,nx]),
 // out_vertices.f32 ([V,3]), out_colors.f32 ([V,3], with colour) and out_faces.i32 ([F,3]).
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path, size_t count) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    if (v.size() != count) { std::fprintf(stderr, "%s: %zu elements, expected %zu\n", path.c_str(), v.size(), count); std::exit(2); }
-    return v;
-}
-static void write_raw(const std::string& path, const torch::Tensor& t) {
-    auto host = t.contiguous().cpu();
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(host.data_ptr()), static_cast<std::streamsize>(host.numel() * host.element_size()));
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
@@ -45,10 +24,7 @@ int main(int argc, char** argv) {
             word != "volume") { std::fprintf(stderr, "bad manifest: volume\n"); return 2; }
         if (!(mf >> word >> nviews >> min_alpha >> min_weight) || word != "views") { std::fprintf(stderr, "bad manifest: views\n"); return 2; }
         auto load = [&](const std::string& name, std::vector<int64_t> shape) {
-            size_t count = 1;
-            for (int64_t s : shape) count *= static_cast<size_t>(s);
-            auto v = read_f32(dir + "/" + name, count);
-            return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+            return load_tensor(dir + "/" + name, shape, torch::kFloat32, dev);
         };
         auto volume = cugs_hip::make_tsdf_volume(origin, nx, ny, nz, vs, trunc, color != 0, dev, max_weight, min_depth);
         std::vector<cugs_hip::TsdfViewInput> views(static_cast<size_t>(nviews));
@@ -62,7 +38,7 @@ int main(int argc, char** argv) {
             }
             v.camera.width = w; v.camera.height = h;
             const std::string stem = "view_" + std::to_string(i);
-            const auto m = read_f32(dir + "/" + stem + "_m.f32", 16);
+            const auto m = read_raw<float>(dir + "/" + stem + "_m.f32", 16);
             for (int k = 0; k < 16; ++k) v.camera.view[k] = m[static_cast<size_t>(k)];
             v.depth_map = load(stem + "_d.f32", {h, w});
             v.alpha = load(stem + "_a.f32", {h, w});

@@ -7,27 +7,7 @@
 // and, when V > 0, {positions,sh,opacities,rotations,scales}.f32 and cameras.f32 (V x 25 floats: view[16] fx fy cx cy
 // width height cam_center[3]).  Writes out_metrics.f32 ([P,4] from eval_metrics), out_psnr.f32 / out_ssim.f32 ([P] from
 // compute_psnr / compute_ssim) and json/eval.json (evaluate(...).save_json, which creates the directory).
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-template <typename T> static std::vector<T> read_raw(const std::string& path, size_t count = 0) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<T> v(static_cast<size_t>(bytes) / sizeof(T));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    if (count && v.size() != count) { std::fprintf(stderr, "%s: %zu elements, expected %zu\n", path.c_str(), v.size(), count); std::exit(2); }
-    return v;
-}
-static void write_f32(const std::string& path, const std::vector<float>& v) {
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(v.data()), v.size() * sizeof(float));
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
@@ -39,13 +19,7 @@ int main(int argc, char** argv) {
         int npairs = 0, nviews = 0, degree = 0;
         if (!(mf >> word >> npairs) || word != "pairs") { std::fprintf(stderr, "bad manifest\n"); return 2; }
         auto image = [&](const std::string& name, int h, int w, bool u8) {
-            const size_t count = static_cast<size_t>(h) * w * 3;
-            if (u8) {
-                auto v = read_raw<uint8_t>(dir + "/" + name, count);
-                return torch::from_blob(v.data(), {h, w, 3}, torch::kUInt8).clone().to(dev);
-            }
-            auto v = read_raw<float>(dir + "/" + name, count);
-            return torch::from_blob(v.data(), {h, w, 3}, torch::kFloat32).clone().to(dev);
+            return load_tensor(dir + "/" + name, {h, w, 3}, u8 ? torch::kUInt8 : torch::kFloat32, dev);
         };
         std::vector<float> metrics, psnr, ssim;
         auto table = torch::full({npairs > 0 ? npairs : 1, 4}, -7.0f, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
@@ -62,9 +36,9 @@ int main(int argc, char** argv) {
             auto host = table.cpu();
             metrics.assign(host.data_ptr<float>(), host.data_ptr<float>() + 4 * npairs);
         }
-        write_f32(dir + "/out_metrics.f32", metrics);
-        write_f32(dir + "/out_psnr.f32", psnr);
-        write_f32(dir + "/out_ssim.f32", ssim);
+        write_raw(dir + "/out_metrics.f32", metrics);
+        write_raw(dir + "/out_psnr.f32", psnr);
+        write_raw(dir + "/out_ssim.f32", ssim);
 
         if (!(mf >> word >> nviews >> degree) || word != "views") { std::fprintf(stderr, "bad manifest\n"); return 2; }
         std::vector<cugs_camera> cameras;
@@ -74,13 +48,7 @@ int main(int argc, char** argv) {
         if (nviews > 0) {
             const auto cw = read_raw<float>(dir + "/cameras.f32", static_cast<size_t>(nviews) * 25);
             for (int v = 0; v < nviews; ++v) {
-                const float* c = cw.data() + 25 * v;
-                cugs_camera cam{};
-                for (int i = 0; i < 16; ++i) cam.view[i] = c[i];
-                cam.fx = c[16]; cam.fy = c[17]; cam.cx = c[18]; cam.cy = c[19];
-                cam.width = static_cast<int>(c[20]); cam.height = static_cast<int>(c[21]);
-                for (int i = 0; i < 3; ++i) cam.cam_center[i] = c[22 + i];
-                cameras.push_back(cam);
+                cameras.push_back(camera_from_words(cw.data() + 25 * v));
                 int h = 0, w = 0;
                 std::string name;
                 mf >> h >> w >> name;
@@ -88,8 +56,7 @@ int main(int argc, char** argv) {
                 names.push_back(name);
             }
             auto load = [&](const char* name, std::vector<int64_t> shape) {
-                auto v = read_raw<float>(dir + "/" + name + ".f32");
-                return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+                return load_tensor(dir + "/" + name + ".f32", shape, torch::kFloat32, dev);
             };
             const int64_t n = static_cast<int64_t>(read_raw<float>(dir + "/opacities.f32").size());
             const int64_t c = static_cast<int64_t>(read_raw<float>(dir + "/sh.f32").size()) / (3 * n);

@@ -8,28 +8,7 @@
 // Writes, per case, out_<i>_out.f32 ({loss, valid weight, valid count}), out_<i>_gd.f32, out_<i>_ga.f32 ([h,w]:
 // dL_ddepth_map, dL_dalpha) and out_<i>_n.f32 ([3,h,w]: the normal map) from normal_loss with the weight and
 // cos_weight 0.7, l1_weight 0.3, and out_<i>_dn.f32 ([3,h,w]) from depth_to_normals.
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path, size_t count) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    if (v.size() != count) { std::fprintf(stderr, "%s: %zu elements, expected %zu\n", path.c_str(), v.size(), count); std::exit(2); }
-    return v;
-}
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto host = t.contiguous().cpu();
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(host.data_ptr<float>()), host.numel() * sizeof(float));
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
@@ -41,10 +20,7 @@ int main(int argc, char** argv) {
         int ncases = 0;
         if (!(mf >> word >> ncases) || word != "cases") { std::fprintf(stderr, "bad manifest\n"); return 2; }
         auto load = [&](const std::string& name, std::vector<int64_t> shape) {
-            size_t count = 1;
-            for (int64_t s : shape) count *= static_cast<size_t>(s);
-            auto v = read_f32(dir + "/" + name, count);
-            return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+            return load_tensor(dir + "/" + name, shape, torch::kFloat32, dev);
         };
         for (int i = 0; i < ncases; ++i) {
             int h = 0, w = 0;
@@ -55,11 +31,11 @@ int main(int argc, char** argv) {
             auto t = load(stem + "_t.f32", {3, h, w});
             const auto r = cugs_hip::normal_loss(d, a, fx, fy, cx, cy, t, wt, 0.7f, 0.3f, 1e-3f, true, true);
             const std::string out = dir + "/out_" + std::to_string(i);
-            write_f32(out + "_out.f32", torch::cat({r.loss.reshape({1}), r.valid_weight.reshape({1}), r.valid_count.reshape({1})}));
-            write_f32(out + "_gd.f32", r.dL_ddepth_map);
-            write_f32(out + "_ga.f32", r.dL_dalpha);
-            write_f32(out + "_n.f32", r.normals);
-            write_f32(out + "_dn.f32", cugs_hip::depth_to_normals(d, a, fx, fy, cx, cy));
+            write_raw(out + "_out.f32", torch::cat({r.loss.reshape({1}), r.valid_weight.reshape({1}), r.valid_count.reshape({1})}));
+            write_raw(out + "_gd.f32", r.dL_ddepth_map);
+            write_raw(out + "_ga.f32", r.dL_dalpha);
+            write_raw(out + "_n.f32", r.normals);
+            write_raw(out + "_dn.f32", cugs_hip::depth_to_normals(d, a, fx, fy, cx, cy));
         }
         bool threw = false;                                       // a prior with both loss weights 0 is a c10::Error
         if (ncases > 0) {

@@ -8,44 +8,14 @@
 //   removed             the return of prune_by_scores(min_max_weight = smallest positive float) with a FusedAdam that
 //                       has taken one step at learning rate 0 (moments set, parameters untouched)
 //   p_{positions,sh,opacities,rotations,scales}, m_0..m_4, v_0..v_4   the pruned model and moments (group order)
-#include "cugs_hip_torch.hpp"
+#include "driver_io.hpp"
 
-#include <cstdio>
-#include <fstream>
 #include <limits>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    return v;
-}
-
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto c = t.detach().to(torch::kCPU).contiguous().to(torch::kFloat32);
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(c.data_ptr<float>()), c.numel() * sizeof(float));
-}
-
-static cugs_camera read_camera(const std::string& path) {
-    const auto words = read_f32(path);
-    cugs_camera cam{};
-    for (int i = 0; i < 16; ++i) cam.view[i] = words[i];
-    cam.fx = words[16]; cam.fy = words[17]; cam.cx = words[18]; cam.cy = words[19];
-    cam.width = static_cast<int>(words[20]); cam.height = static_cast<int>(words[21]);
-    for (int i = 0; i < 3; ++i) cam.cam_center[i] = words[22 + i];
-    return cam;
-}
 
 static void write_scores(const std::string& dir, const char* tag, const cugs_hip::ContributionScores& s) {
-    write_f32(dir + "/" + tag + "_sum.f32", s.weight_sum());
-    write_f32(dir + "/" + tag + "_max.f32", s.weight_max());
-    write_f32(dir + "/" + tag + "_count.f32", s.pixel_count());         // exact in float32 below 2^24
+    write_as_f32(dir + "/" + tag + "_sum.f32", s.weight_sum());
+    write_as_f32(dir + "/" + tag + "_max.f32", s.weight_max());
+    write_as_f32(dir + "/" + tag + "_count.f32", s.pixel_count());         // exact in float32 below 2^24
 }
 
 int main(int argc, char** argv) {
@@ -53,12 +23,11 @@ int main(int argc, char** argv) {
     const std::string dir = argv[1];
     const auto dev = torch::Device(torch::kCUDA, 0);
     auto load = [&](const char* name, std::vector<int64_t> shape) {
-        auto v = read_f32(dir + "/" + name + ".f32");
-        return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+        return load_tensor(dir + "/" + name + ".f32", shape, torch::kFloat32, dev);
     };
     const std::vector<cugs_camera> cams{read_camera(dir + "/camera0.f32"), read_camera(dir + "/camera1.f32")};
-    const int64_t n = static_cast<int64_t>(read_f32(dir + "/opacities.f32").size());
-    const int64_t c = static_cast<int64_t>(read_f32(dir + "/sh.f32").size()) / (3 * n);
+    const int64_t n = static_cast<int64_t>(read_raw<float>(dir + "/opacities.f32").size());
+    const int64_t c = static_cast<int64_t>(read_raw<float>(dir + "/sh.f32").size()) / (3 * n);
     const int w = cams[0].width, h = cams[0].height;
     cugs_hip::ModelTensors model{load("positions", {n, 3}), load("sh", {n, 3, c}), load("opacities", {n, 1}),
                                  load("rotations", {n, 4}), load("scales", {n, 3})};
@@ -88,15 +57,15 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "the pruned model and optimizer disagree\n");
         return 1;
     }
-    write_f32(dir + "/removed.f32", torch::full({1}, static_cast<double>(removed)));
-    write_f32(dir + "/p_positions.f32", model.positions);
-    write_f32(dir + "/p_sh.f32", model.sh_coeffs);
-    write_f32(dir + "/p_opacities.f32", model.opacities);
-    write_f32(dir + "/p_rotations.f32", model.rotations);
-    write_f32(dir + "/p_scales.f32", model.scales);
+    write_as_f32(dir + "/removed.f32", torch::full({1}, static_cast<double>(removed)));
+    write_as_f32(dir + "/p_positions.f32", model.positions);
+    write_as_f32(dir + "/p_sh.f32", model.sh_coeffs);
+    write_as_f32(dir + "/p_opacities.f32", model.opacities);
+    write_as_f32(dir + "/p_rotations.f32", model.rotations);
+    write_as_f32(dir + "/p_scales.f32", model.scales);
     for (int g = 0; g < 5; ++g) {
-        write_f32(dir + "/m_" + std::to_string(g) + ".f32", opt.exp_avg()[g]);
-        write_f32(dir + "/v_" + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
+        write_as_f32(dir + "/m_" + std::to_string(g) + ".f32", opt.exp_avg()[g]);
+        write_as_f32(dir + "/v_" + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
     }
     std::printf("scores_driver ok: n %lld, %dx%d, removed %lld\n", static_cast<long long>(n), w, h,
                 static_cast<long long>(removed));

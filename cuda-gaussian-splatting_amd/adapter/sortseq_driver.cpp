@@ -7,39 +7,9 @@
 // file holds the cugs_camera words: view[16] fx fy cx cy width height cam_center[3]; C coefficients per channel) and
 // writes, per frame i (from 0), <dir>/frame<i>.color.f32 (the image's float32 bits), frame<i>.indices.i32 and
 // frame<i>.ranges.i32 (raw int32), and prints "frame <i> <scene> pairs=<P>".
-#include "cugs_hip_torch.hpp"
+#include "driver_io.hpp"
 
-#include <cstdio>
-#include <fstream>
 #include <map>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    return v;
-}
-
-static void write_raw(const std::string& path, const torch::Tensor& t) {
-    auto c = t.detach().to(torch::kCPU).contiguous();
-    std::ofstream f(path, std::ios::binary);
-    f.write(static_cast<const char*>(c.data_ptr()), static_cast<std::streamsize>(c.numel() * c.element_size()));
-}
-
-static cugs_camera read_camera(const std::string& path) {
-    const auto words = read_f32(path);
-    cugs_camera cam{};
-    for (int i = 0; i < 16; ++i) cam.view[i] = words[i];
-    cam.fx = words[16]; cam.fy = words[17]; cam.cx = words[18]; cam.cy = words[19];
-    cam.width = static_cast<int>(words[20]); cam.height = static_cast<int>(words[21]);
-    for (int i = 0; i < 3; ++i) cam.cam_center[i] = words[22 + i];
-    return cam;
-}
 
 struct Scene { cugs_hip::ModelTensors model; cugs_camera cam; };
 
@@ -55,7 +25,7 @@ int main(int argc, char** argv) {
             auto it = scenes.find(name);
             if (it != scenes.end()) return it->second;
             auto load = [&](const char* what, int64_t cols) {
-                auto v = read_f32(dir + "/" + name + "." + what + ".f32");
+                auto v = read_raw<float>(dir + "/" + name + "." + what + ".f32");
                 const int64_t rows = static_cast<int64_t>(v.size()) / cols;
                 return torch::from_blob(v.data(), {rows, cols}, torch::kFloat32).clone().to(dev);
             };

@@ -9,49 +9,18 @@
 //   b_{positions,sh,opacities,rotations,scales}, b_m_0..4, b_v_0..4, b_means_2d
 //                                              one render_backward(..., sparse_adam = true) on a copy of the model
 // and prints whether sparse_adam without the FusedAdam, and with an MCMCController, were refused.
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <fstream>
-#include <string>
-#include <vector>
-
-static std::vector<float> read_f32(const std::string& path) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<float> v(static_cast<size_t>(bytes) / sizeof(float));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    return v;
-}
-
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto c = t.detach().to(torch::kCPU).contiguous().to(torch::kFloat32);
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(c.data_ptr<float>()), c.numel() * sizeof(float));
-}
-
-static cugs_camera read_camera(const std::string& path) {
-    const auto words = read_f32(path);
-    cugs_camera cam{};
-    for (int i = 0; i < 16; ++i) cam.view[i] = words[i];
-    cam.fx = words[16]; cam.fy = words[17]; cam.cx = words[18]; cam.cy = words[19];
-    cam.width = static_cast<int>(words[20]); cam.height = static_cast<int>(words[21]);
-    for (int i = 0; i < 3; ++i) cam.cam_center[i] = words[22 + i];
-    return cam;
-}
+#include "driver_io.hpp"
 
 static void write_state(const std::string& dir, const std::string& tag, const cugs_hip::ModelTensors& m,
                         const cugs_hip::FusedAdam& opt) {
-    write_f32(dir + "/" + tag + "_positions.f32", m.positions);
-    write_f32(dir + "/" + tag + "_sh.f32", m.sh_coeffs);
-    write_f32(dir + "/" + tag + "_opacities.f32", m.opacities);
-    write_f32(dir + "/" + tag + "_rotations.f32", m.rotations);
-    write_f32(dir + "/" + tag + "_scales.f32", m.scales);
+    write_as_f32(dir + "/" + tag + "_positions.f32", m.positions);
+    write_as_f32(dir + "/" + tag + "_sh.f32", m.sh_coeffs);
+    write_as_f32(dir + "/" + tag + "_opacities.f32", m.opacities);
+    write_as_f32(dir + "/" + tag + "_rotations.f32", m.rotations);
+    write_as_f32(dir + "/" + tag + "_scales.f32", m.scales);
     for (int g = 0; g < 5; ++g) {
-        write_f32(dir + "/" + tag + "_m_" + std::to_string(g) + ".f32", opt.exp_avg()[g]);
-        write_f32(dir + "/" + tag + "_v_" + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
+        write_as_f32(dir + "/" + tag + "_m_" + std::to_string(g) + ".f32", opt.exp_avg()[g]);
+        write_as_f32(dir + "/" + tag + "_v_" + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
     }
 }
 
@@ -60,13 +29,12 @@ int main(int argc, char** argv) {
     const std::string dir = argv[1];
     const auto dev = torch::Device(torch::kCUDA, 0);
     auto load = [&](const char* name, std::vector<int64_t> shape) {
-        auto v = read_f32(dir + "/" + name + ".f32");
-        return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+        return load_tensor(dir + "/" + name + ".f32", shape, torch::kFloat32, dev);
     };
     try {
         const cugs_camera cam = read_camera(dir + "/camera.f32");
-        const int64_t n = static_cast<int64_t>(read_f32(dir + "/opacities.f32").size());
-        const int64_t c = static_cast<int64_t>(read_f32(dir + "/sh.f32").size()) / (3 * n);
+        const int64_t n = static_cast<int64_t>(read_raw<float>(dir + "/opacities.f32").size());
+        const int64_t c = static_cast<int64_t>(read_raw<float>(dir + "/sh.f32").size()) / (3 * n);
         const int w = cam.width, h = cam.height;
         cugs_hip::ModelTensors a{load("positions", {n, 3}), load("sh", {n, 3, c}), load("opacities", {n, 1}),
                                  load("rotations", {n, 4}), load("scales", {n, 3})};
@@ -78,7 +46,7 @@ int main(int argc, char** argv) {
 
         // (a) the stand-alone masked step on given gradients: the same bytes as the Python host
         auto out = cugs_hip::render(a, cam, settings);
-        write_f32(dir + "/radii.f32", out.radii);
+        write_as_f32(dir + "/radii.f32", out.radii);
         cugs_hip::FusedAdam opt({a.positions, a.sh_coeffs, a.opacities, a.scales, a.rotations}, lrs);
         cugs_hip::BackwardOutput g;
         g.dL_dpositions = load("g_positions", {n, 3}); g.dL_dsh_coeffs = load("g_sh", {n, 3, c});
@@ -98,7 +66,7 @@ int main(int argc, char** argv) {
                                              {}, {}, false, false, /*sparse_adam=*/true);
         torch::cuda::synchronize();
         write_state(dir, "b", b, opt2);
-        write_f32(dir + "/b_means_2d.f32", res.dL_dmeans_2d);
+        write_as_f32(dir + "/b_means_2d.f32", res.dL_dmeans_2d);
 
         // the refusals leave the model alone
         const auto before = b.positions.clone();

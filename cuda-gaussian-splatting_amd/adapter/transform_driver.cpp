@@ -9,48 +9,14 @@
 //   t_{positions,sh,opacities,rotations,scales}, tm_0..4, tv_0..4   model and moments (group order) after one FusedAdam
 //                       step at learning rate 0 (moments set, parameters untouched) and the masked transform_gaussians
 //   p_{...}, m_0..4, v_0..4                                         the same after merge_gaussians(model, other, &opt)
-#include "cugs_hip_torch.hpp"
-
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-
-template <typename T>
-static std::vector<T> read_raw(const std::string& path) {
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); std::exit(2); }
-    const std::streamsize bytes = f.tellg();
-    f.seekg(0);
-    std::vector<T> v(static_cast<size_t>(bytes) / sizeof(T));
-    f.read(reinterpret_cast<char*>(v.data()), bytes);
-    return v;
-}
-
-static void write_f32(const std::string& path, const torch::Tensor& t) {
-    auto c = t.detach().to(torch::kCPU).contiguous().to(torch::kFloat32);
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(c.data_ptr<float>()), c.numel() * sizeof(float));
-}
-
-static cugs_camera read_camera(const std::string& path) {
-    const auto words = read_raw<float>(path);
-    cugs_camera cam{};
-    for (int i = 0; i < 16; ++i) cam.view[i] = words[i];
-    cam.fx = words[16]; cam.fy = words[17]; cam.cx = words[18]; cam.cy = words[19];
-    cam.width = static_cast<int>(words[20]); cam.height = static_cast<int>(words[21]);
-    for (int i = 0; i < 3; ++i) cam.cam_center[i] = words[22 + i];
-    return cam;
-}
+#include "driver_io.hpp"
 
 int main(int argc, char** argv) {
     if (argc != 2) { std::fprintf(stderr, "usage: %s <dir>\n", argv[0]); return 2; }
     const std::string dir = argv[1];
     const auto dev = torch::Device(torch::kCUDA, 0);
     auto load = [&](const std::string& name, std::vector<int64_t> shape) {
-        auto v = read_raw<float>(dir + "/" + name + ".f32");
-        return torch::from_blob(v.data(), shape, torch::kFloat32).clone().to(dev);
+        return load_tensor(dir + "/" + name + ".f32", shape, torch::kFloat32, dev);
     };
     auto load_model = [&](const std::string& prefix) {
         const int64_t n = static_cast<int64_t>(read_raw<float>(dir + "/" + prefix + "opacities.f32").size());
@@ -65,14 +31,14 @@ int main(int argc, char** argv) {
     const auto other = load_model("o_");
     const int64_t n = model.positions.size(0);
     const auto mask = load("mask", {n}).ne(0.0f);
-    const auto words = read_raw<double>(dir + "/sim.f64");
+    const auto words = read_raw<double>(dir + "/sim.f64", 13);
     cugs_hip::Similarity sim;
     sim.scale = words[0];
     for (int i = 0; i < 9; ++i) sim.rotation[i] = words[1 + i];
     for (int i = 0; i < 3; ++i) sim.translation[i] = words[10 + i];
 
     const cugs_camera moved = cugs_hip::transform_camera(cam, sim);
-    write_f32(dir + "/camera_moved.f32", torch::from_blob(const_cast<float*>(moved.view), {16}, torch::kFloat32).clone());
+    write_as_f32(dir + "/camera_moved.f32", torch::from_blob(const_cast<float*>(moved.view), {16}, torch::kFloat32).clone());
     const auto round_trip = sim.compose(sim.inverse()).matrix();
     for (int i = 0; i < 16; ++i)
         if (std::abs(round_trip[i] - (i % 5 == 0 ? 1.0 : 0.0)) > 1e-12) { std::fprintf(stderr, "compose(inverse) is not I\n"); return 1; }
@@ -86,14 +52,14 @@ int main(int argc, char** argv) {
     opt.step();
 
     auto dump = [&](const std::string& p, const std::string& mname, const std::string& vname) {
-        write_f32(dir + "/" + p + "positions.f32", model.positions);
-        write_f32(dir + "/" + p + "sh.f32", model.sh_coeffs);
-        write_f32(dir + "/" + p + "opacities.f32", model.opacities);
-        write_f32(dir + "/" + p + "rotations.f32", model.rotations);
-        write_f32(dir + "/" + p + "scales.f32", model.scales);
+        write_as_f32(dir + "/" + p + "positions.f32", model.positions);
+        write_as_f32(dir + "/" + p + "sh.f32", model.sh_coeffs);
+        write_as_f32(dir + "/" + p + "opacities.f32", model.opacities);
+        write_as_f32(dir + "/" + p + "rotations.f32", model.rotations);
+        write_as_f32(dir + "/" + p + "scales.f32", model.scales);
         for (int g = 0; g < 5; ++g) {
-            write_f32(dir + "/" + mname + std::to_string(g) + ".f32", opt.exp_avg()[g]);
-            write_f32(dir + "/" + vname + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
+            write_as_f32(dir + "/" + mname + std::to_string(g) + ".f32", opt.exp_avg()[g]);
+            write_as_f32(dir + "/" + vname + std::to_string(g) + ".f32", opt.exp_avg_sq()[g]);
         }
     };
     const auto* before = model.positions.data_ptr<float>();

@@ -1,25 +1,19 @@
 """The bilateral-grid slice, backward and TV regulariser through the C++ host (cuda-gaussian-splatting_amd/adapter:
 cugs_hip::bilagrid_slice / bilagrid_slice_backward / bilagrid_tv) run as a native program (adapter/bilagrid_driver.bin)
 on the same raw inputs as the Python host: the same bytes in every output."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import bilagrid_ref as br
+from cpp_driver import run_driver
 from util import np_
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "bilagrid_driver.bin")
 TV_WEIGHT = 2.5
 
 
 def test_cpp_bilagrid_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("bilagrid_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     cases = [br.CASES[0], br.CASES[2], br.CASES[5]]           # 7x5 / (4,3,2), 37x53 / (16,16,8), 24x40 / (5,3,4) with the clamp
     manifest = [f"cases {len(cases)}"]
     for i, c in enumerate(cases):
@@ -29,8 +23,7 @@ def test_cpp_bilagrid_matches_python_host(pkg, dev, tmp_path):
         manifest.append(f"{h} {w} {l} {gy} {gx} {TV_WEIGHT}")
     (tmp_path / "manifest.txt").write_text("\n".join(manifest) + "\n")
 
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("bilagrid_driver", tmp_path)
     assert f"bilagrid_driver ok cases={len(cases)} bad_grid_throws=1" in res.stdout
 
     for i, c in enumerate(cases):

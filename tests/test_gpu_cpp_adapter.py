@@ -1,23 +1,17 @@
 """The C++ host side (cuda-gaussian-splatting_amd/adapter: libtorch layer over the C ABI, the code a
 maintainer links under the reference's own render()/render_backward()/FusedAdam calls) run as a native
 program on the same raw inputs as the Python mirror: same kernels, so identical forward results."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+from cpp_driver import NO_LEGACY_IPC, run_driver
 from util import max_err_over_max, np_
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "adapter_driver.bin")
 
 
 def test_cpp_adapter_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("adapter_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     w, h, n, deg = 200, 150, 5000, 3
     arrays = pkg.scene.make_gaussians(n, w, h, sh_degree=deg, seed=17, mu_s=-3.8)
     cam = pkg.scene.make_camera(w, h, view=1)
@@ -33,10 +27,7 @@ def test_cpp_adapter_matches_python_host(pkg, dev, tmp_path):
     noise = torch.randn((2, n, 3), generator=torch.Generator().manual_seed(11))
     noise.numpy().tofile(tmp_path / "split_noise.bin")
 
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([DRIVER, str(tmp_path), str(n), "16", str(w), str(h)], capture_output=True, text=True,
-                         timeout=300, env=env)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("adapter_driver", tmp_path, n, "16", w, h, env=NO_LEGACY_IPC)
     assert "torch_check=1" in res.stdout                     # TORCH_CHECK -> c10::Error on a CPU tensor
     # reference-glue path: a RenderOutput without the packed scratch (the reference's struct has no field for it)
     # gets the records rebuilt and runs the same packed blend kernel: same gradients up to atomic order

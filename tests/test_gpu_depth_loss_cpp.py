@@ -1,24 +1,18 @@
 """The depth-supervision loss through the C++ host (cuda-gaussian-splatting_amd/adapter: cugs_hip::depth_loss) run as a
 native program (adapter/depth_loss_driver.bin) on the same raw inputs as the Python host, with a weight map and a
 fitted alignment, in both spaces: the same bytes in every output."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import depth_loss_ref as dr
+from cpp_driver import run_driver
 from util import np_
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "depth_loss_driver.bin")
 
 
 def test_cpp_depth_loss_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("depth_loss_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     cases = [(h, w, inv) for (h, w) in [(7, 5), (37, 53), (64, 64)] for inv in (False, True)]
     manifest = [f"cases {len(cases)}"]
     for i, (h, w, inv) in enumerate(cases):
@@ -28,8 +22,7 @@ def test_cpp_depth_loss_matches_python_host(pkg, dev, tmp_path):
         manifest.append(f"{h} {w} {int(inv)}")
     (tmp_path / "manifest.txt").write_text("\n".join(manifest) + "\n")
 
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("depth_loss_driver", tmp_path)
     assert f"depth_loss_driver ok cases={len(cases)} bad_args_throw=1" in res.stdout
 
     for i, (h, w, inv) in enumerate(cases):

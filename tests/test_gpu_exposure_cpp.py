@@ -1,23 +1,17 @@
 """The exposure-compensated, masked loss through the C++ host (cuda-gaussian-splatting_amd/adapter:
 cugs_hip::combined_loss_exposure) run as a native program (adapter/exposure_driver.bin) on the same raw inputs as the
 Python host: the same bytes in every output."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import exposure_ref as er
+from cpp_driver import run_driver
 from util import np_
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "exposure_driver.bin")
 
 
 def test_cpp_exposure_loss_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("exposure_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     shapes = [(7, 5), (37, 53), (64, 64)]
     manifest = [f"cases {len(shapes)}"]
     for i, (h, w) in enumerate(shapes):
@@ -27,8 +21,7 @@ def test_cpp_exposure_loss_matches_python_host(pkg, dev, tmp_path):
         manifest.append(f"{h} {w} 1 0.2")
     (tmp_path / "manifest.txt").write_text("\n".join(manifest) + "\n")
 
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("exposure_driver", tmp_path)
     assert f"exposure_driver ok cases={len(shapes)} bad_exposure_throws=1" in res.stdout
 
     for i, (h, w) in enumerate(shapes):

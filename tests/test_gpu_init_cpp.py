@@ -1,32 +1,24 @@
 """The point-cloud initialisation through the C++ host (cuda-gaussian-splatting_amd/adapter: cugs_hip::
 init_gaussians_from_sparse / knn_mean_distances) run as a native program (adapter/init_driver.bin) on the same raw inputs
 as the Python host: identical bits, on every route."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import init_ref as ir
+from cpp_driver import run_driver
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "init_driver.bin")
 NAMES = ("positions", "sh_coeffs", "opacities", "rotations", "scales")
 
 
 @pytest.mark.parametrize("route", ("auto", "exhaustive", "tree"))
 def test_cpp_init_matches_python_host(pkg, dev, tmp_path, route):
-    if not os.path.exists(DRIVER):
-        pytest.skip("init_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     from cugs_amd import gaussian_init
     n, degree, k = 30000, 2, 4
     pos, col = ir.make_cloud("blobs", n, seed=71)
     pos.tofile(tmp_path / "positions.bin")
     col.tofile(tmp_path / "colors.bin")
-    res = subprocess.run([DRIVER, str(tmp_path), str(n), str(degree), str(k), str(gaussian_init.ROUTES[route])],
-                         capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("init_driver", tmp_path, n, degree, k, gaussian_init.ROUTES[route])
     assert f"init_driver ok n={n} coeffs=9 cuda=1 bad_degree_throws=1 empty=0" in res.stdout
 
     model = pkg.init_gaussians_from_sparse(pos, col, sh_degree=degree, k_neighbors=k, device=dev, route=route)

@@ -1,27 +1,20 @@
 """Pixel maps lifted onto Gaussians through the C++ host (adapter/lift_driver.cpp: cugs_hip::lift_pixel_maps, lift_maps,
 vote_labels, error_scores, select_gaussians over ModelTensors / FusedAdam) against the Python host on the same inputs,
 and against the reference of tests/lift_ref.py."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import lift_ref
+from cpp_driver import NO_LEGACY_IPC, read_f32, run_driver, write_camera, write_f32
 from scores_ref import scene
 from util import max_err_over_max, np_
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "lift_driver.bin")
 KEY, IMAGE, KEEP = "40x24", "grid", 4
 
 
 def test_cpp_lift_driver_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("lift_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     s0, s1 = scene(KEY, 0), scene(KEY, 1)
     arrays, n, w, h = s0["arrays"], s0["n"], s0["w"], s0["h"]
     cams = (s0["cam"], s1["cam"])
@@ -32,16 +25,11 @@ def test_cpp_lift_driver_matches_python_host(pkg, dev, tmp_path):
                  rotations=arrays["rotations"], scales=arrays["scales"], dl_dcolor=g, labels=lab,
                  map0=lift_ref.float_map(KEY, 0, 4), map1=lift_ref.float_map(KEY, 1, 4),
                  err0=lift_ref.error_map(KEY, 0), err1=lift_ref.error_map(KEY, 1))
-    for k, v in files.items():
-        np.ascontiguousarray(v, np.float32).tofile(tmp_path / f"{k}.f32")
+    write_f32(tmp_path, **files)
     for i, cam in enumerate(cams):
-        abi = cam.to_abi()
-        np.array(list(abi.view) + [abi.fx, abi.fy, abi.cx, abi.cy, abi.width, abi.height] + list(abi.cam_center),
-                 np.float32).tofile(tmp_path / f"camera{i}.f32")
-    res = subprocess.run([DRIVER, str(tmp_path), str(num), str(KEEP)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
-    rd = lambda name: np.fromfile(tmp_path / f"{name}.f32", dtype=np.float32)
+        write_camera(tmp_path / f"camera{i}.f32", cam)
+    run_driver("lift_driver", tmp_path, num, KEEP, env=NO_LEGACY_IPC)
+    rd = lambda name: read_f32(tmp_path, name)
 
     # the same in the Python host
     from cugs_amd.fused_adam import AdamConfig, PositionLRConfig

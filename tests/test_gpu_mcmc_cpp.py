@@ -2,22 +2,17 @@
 render_backward(..., FusedAdam*, const MCMCController*, step)) run as a native program (adapter/mcmc_driver.bin) on
 the same raw inputs as the Python mirror: regulariser + FusedAdam step + position noise + relocation give the same
 bytes; the fused route through render_backward agrees up to the blend backward's atomic summation order."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+from cpp_driver import run_driver
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "mcmc_driver.bin")
 NAMES = ("positions", "sh_coeffs", "opacities", "rotations", "scales")
 
 
 def test_cpp_mcmc_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("mcmc_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     w, h, n, deg = 200, 150, 5000, 3
     arrays = pkg.scene.make_gaussians(n, w, h, sh_degree=deg, seed=23, mu_s=-3.8)
     arrays["opacities"][::5] = -7.0                                  # a fifth dead: relocation has work
@@ -33,9 +28,7 @@ def test_cpp_mcmc_matches_python_host(pkg, dev, tmp_path):
     abi = cam.to_abi()
     np.array(list(abi.view) + [abi.fx, abi.fy, abi.cx, abi.cy] + list(abi.cam_center) + bg,
              np.float32).tofile(tmp_path / "camera.bin")
-    res = subprocess.run([DRIVER, str(tmp_path), str(n), "16", str(w), str(h)], capture_output=True, text=True,
-                         timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("mcmc_driver", tmp_path, n, "16", w, h)
     assert "fused_grads_undefined=1 needs_fused=1" in res.stdout
 
     # the Python mirror of the same configuration (mcmc_driver.cpp); noise_lr_max_steps = 1 keeps the schedule at its

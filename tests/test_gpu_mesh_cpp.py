@@ -2,7 +2,6 @@
 as a native program (adapter/mesh_driver.bin) on the fused sphere of tests/tsdf_cases.py: the bytes of the Python host in
 the planes, the vertices, the colours and the faces."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,16 +11,13 @@ import torch            # before the package, as in every GPU test module: its l
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import tsdf_cases as cases      # noqa: E402
 import tsdf_ref as R            # noqa: E402
+from cpp_driver import run_driver
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "mesh_driver.bin")
 
 
 @pytest.mark.parametrize("box,color", [("odd", True), ("aligned", False)])
 def test_cpp_mesh_matches_python_host(pkg, dev, tmp_path, box, color):
-    if not os.path.exists(DRIVER):
-        pytest.skip("mesh_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     dims, origin = cases.BOXES[box]
     views = cases.sphere_views(color)
     flt = lambda x: repr(float(np.float32(x)))               # the float32 values, written so that they read back exactly
@@ -39,8 +35,7 @@ def test_cpp_mesh_matches_python_host(pkg, dev, tmp_path, box, color):
             v["weight"].tofile(tmp_path / f"view_{i}_w.f32")
     (tmp_path / "manifest.txt").write_text("\n".join(manifest) + "\n")
 
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("mesh_driver", tmp_path)
 
     up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     cam = lambda v: pkg.CameraInfo(width=v["W"], height=v["H"],

@@ -2,25 +2,20 @@
 compute_psnr / compute_ssim / evaluate) run as a native program (adapter/metrics_driver.bin) on the same raw inputs as
 the Python host: identical rows, PSNR within a few ulp of log10f, the reference's JSON document."""
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import metrics_ref as mr
+from cpp_driver import camera_words, run_driver
 from util import np_
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "metrics_driver.bin")
 KEYS = {"mean_psnr", "mean_ssim", "num_gaussians", "sh_degree", "eval_time_seconds", "num_test_images", "per_image"}
 W, H, N = 160, 120, 400
 
 
 def test_cpp_metrics_match_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("metrics_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     # image pairs: float targets on three shapes, 8-bit targets on two
     pairs = []
     for (h, w), u8 in (((7, 5), False), ((37, 53), False), ((270, 480), False), ((37, 53), True), ((64, 64), True)):
@@ -48,16 +43,14 @@ def test_cpp_metrics_match_python_host(pkg, dev, tmp_path):
         cache.add(img)
         img.numpy().tofile(tmp_path / f"view_{v}.u8")
         manifest.append(f"{img.shape[0]} {img.shape[1]} {names[v]}")
-        abi = cam.to_abi()
-        cam_words += list(abi.view) + [abi.fx, abi.fy, abi.cx, abi.cy, abi.width, abi.height] + list(abi.cam_center)
-    np.array(cam_words, np.float32).tofile(tmp_path / "cameras.f32")
+        cam_words.append(camera_words(cam))
+    np.concatenate(cam_words).tofile(tmp_path / "cameras.f32")
     for k, name in (("positions", "positions"), ("sh_coeffs", "sh"), ("opacities", "opacities"), ("rotations", "rotations"),
                     ("scales", "scales")):
         np.ascontiguousarray(arrays[k], np.float32).tofile(tmp_path / f"{name}.f32")
     (tmp_path / "manifest.txt").write_text("\n".join(manifest) + "\n")
 
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("metrics_driver", tmp_path)
     assert f"metrics_driver ok pairs={len(pairs)} views=3 shape_mismatch_throws=1" in res.stdout
 
     rows = np.fromfile(tmp_path / "out_metrics.f32", np.float32).reshape(len(pairs), 4)

@@ -1,24 +1,18 @@
 """The normal-supervision loss through the C++ host (cuda-gaussian-splatting_amd/adapter: cugs_hip::normal_loss and
 depth_to_normals) run as a native program (adapter/normal_loss_driver.bin) on the same raw inputs as the Python host,
 with a weight map and both distances: the same bytes in every output."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import normal_loss_ref as nr
+from cpp_driver import run_driver
 from util import np_
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "normal_loss_driver.bin")
 
 
 def test_cpp_normal_loss_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("normal_loss_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     from cugs_amd.types import CameraInfo, CameraIntrinsics
     cases = [(5, 7), (37, 53), (19, 70)]
     manifest = [f"cases {len(cases)}"]
@@ -30,8 +24,7 @@ def test_cpp_normal_loss_matches_python_host(pkg, dev, tmp_path):
         manifest.append(f"{h} {w} " + " ".join(repr(float(np.float32(c[k]))) for k in ("fx", "fy", "cx", "cy")))
     (tmp_path / "manifest.txt").write_text("\n".join(manifest) + "\n")
 
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("normal_loss_driver", tmp_path)
     assert f"normal_loss_driver ok cases={len(cases)} bad_args_throw=1" in res.stdout
 
     for i, (h, w) in enumerate(cases):

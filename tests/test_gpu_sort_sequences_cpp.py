@@ -3,38 +3,27 @@
 on the held capacity, wide (the -1 miss), wide again, an in-range view inside the hold - through
 adapter/sortseq_driver.cpp.  Every frame's image and index list must be the Python host's, bit for bit, which
 tests/test_gpu_sort_sequences.py ties to the oracle (and which is checked against it here once more)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from test_gpu_sort_sequences import DEG, _Spy, _Stream, scene
+from cpp_driver import NO_LEGACY_IPC, run_driver, write_camera
 from util import np_
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "sortseq_driver.bin")
 SCRIPT = ("S", "D", "S", "W", "W", "S")
 
 
 def test_cpp_host_recovers_over_the_same_sequence(pkg, dev, tmp_path, monkeypatch):
-    if not os.path.exists(DRIVER):
-        pytest.skip("sortseq_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     for name in set(SCRIPT):
         sc = scene(name)
         a = sc["arrays"]
         for stem, v in (("positions", a["positions"]), ("sh", a["sh_coeffs"]), ("opacities", a["opacities"]),
                         ("rotations", a["rotations"]), ("scales", a["scales"])):
             np.ascontiguousarray(v, np.float32).tofile(tmp_path / f"{name}.{stem}.f32")
-        abi = sc["cam"].to_abi()
-        np.array(list(abi.view) + [abi.fx, abi.fy, abi.cx, abi.cy, abi.width, abi.height] + list(abi.cam_center),
-                 np.float32).tofile(tmp_path / f"{name}.camera.f32")
+        write_camera(tmp_path / f"{name}.camera.f32", sc["cam"])
     coeffs = (DEG + 1) ** 2
-    res = subprocess.run([DRIVER, str(tmp_path), str(coeffs), *SCRIPT], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    res = run_driver("sortseq_driver", tmp_path, coeffs, *SCRIPT, env=NO_LEGACY_IPC)
     assert "sortseq_driver ok" in res.stdout
 
     # the same script through the Python host (checked there against the oracle and the model, frame by frame)

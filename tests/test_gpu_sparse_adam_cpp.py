@@ -3,28 +3,21 @@ render_backward(..., sparse_adam = true)) against the Python host on the same ra
 gradients gives the same bytes.  The fused route ran its own backward blend, whose float atomics may sum in another
 order than the Python host's: there the rows the view does not see are compared bit for bit (they keep the bytes of
 the input) and the stepped rows up to that order, as tests/test_gpu_mcmc_cpp.py does."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+from cpp_driver import NO_LEGACY_IPC, read_f32, run_driver, write_camera
 from sparse_adam_ref import standard_invisible
 from util import np_
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "sparse_adam_driver.bin")
 FILES = (("positions", "positions"), ("sh", "sh_coeffs"), ("opacities", "opacities"), ("rotations", "rotations"),
          ("scales", "scales"))
 GROUPS = ("positions", "sh_coeffs", "opacities", "scales", "rotations")          # ParamGroup order
 
 
 def test_cpp_sparse_adam_driver_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("sparse_adam_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     n, w, h, deg = 1301, 128, 96, 3
     arrays = pkg.scene.make_gaussians(n, w, h, sh_degree=deg, seed=31, mu_s=-3.7)
     inv = standard_invisible(n)
@@ -37,14 +30,10 @@ def test_cpp_sparse_adam_driver_matches_python_host(pkg, dev, tmp_path):
         np.ascontiguousarray(arrays[k], np.float32).tofile(tmp_path / f"{f}.f32")
         grads[k].tofile(tmp_path / f"g_{f}.f32")
     g.tofile(tmp_path / "dl_dcolor.f32")
-    abi = cam.to_abi()
-    np.array(list(abi.view) + [abi.fx, abi.fy, abi.cx, abi.cy, abi.width, abi.height] + list(abi.cam_center),
-             np.float32).tofile(tmp_path / "camera.f32")
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
+    write_camera(tmp_path / "camera.f32", cam)
+    res = run_driver("sparse_adam_driver", tmp_path, env=NO_LEGACY_IPC)
     assert "fused_grads_undefined=1 needs_fused=1 no_mcmc=1 untouched=1" in res.stdout, res.stdout
-    rd = lambda name: np.fromfile(tmp_path / f"{name}.f32", dtype=np.float32)
+    rd = lambda name: read_f32(tmp_path, name)
 
     settings = pkg.RenderSettings(background=[0.0, 0.0, 0.0], active_sh_degree=deg)
     model = pkg.scene.to_model({k: v.copy() for k, v in arrays.items()}, dev)

@@ -1,26 +1,19 @@
 """The similarity transform and the merge through the C++ host (adapter/transform_driver.cpp: cugs_hip::Similarity,
 transform_camera, transform_gaussians, merge_gaussians over ModelTensors / FusedAdam) against the Python host on the
 same files: parameters bit for bit, moments zero in the same places."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 import transform_ref as tr
+from cpp_driver import NO_LEGACY_IPC, read_f32, run_driver, write_camera
 from util import max_err_over_max, np_
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "cuda-gaussian-splatting_amd", "adapter", "transform_driver.bin")
 FILES = dict(positions="positions", sh="sh_coeffs", opacities="opacities", rotations="rotations", scales="scales")
 
 
 def test_cpp_transform_driver_matches_python_host(pkg, dev, tmp_path):
-    if not os.path.exists(DRIVER):
-        pytest.skip("transform_driver.bin not built (make -C cuda-gaussian-splatting_amd/adapter)")
     w, h, n = tr.W, tr.H, 900
     arrays = pkg.scene.make_gaussians(n, w, h, sh_degree=3, seed=81, mu_s=-3.0)
     other = pkg.scene.make_gaussians(250, w, h, sh_degree=1, seed=82, mu_s=-3.0)
@@ -34,13 +27,9 @@ def test_cpp_transform_driver_matches_python_host(pkg, dev, tmp_path):
     g.tofile(tmp_path / "dl_dcolor.f32")
     mask.astype(np.float32).tofile(tmp_path / "mask.f32")
     np.concatenate([[sim.scale], sim.rotation.reshape(9), sim.translation]).astype(np.float64).tofile(tmp_path / "sim.f64")
-    abi = cam.to_abi()
-    np.array(list(abi.view) + [abi.fx, abi.fy, abi.cx, abi.cy, abi.width, abi.height] + list(abi.cam_center),
-             np.float32).tofile(tmp_path / "camera0.f32")
-    res = subprocess.run([DRIVER, str(tmp_path)], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
-    assert res.returncode == 0, f"rc={res.returncode} stdout={res.stdout!r} stderr={res.stderr!r}"
-    rd = lambda name: np.fromfile(tmp_path / f"{name}.f32", dtype=np.float32)
+    write_camera(tmp_path / "camera0.f32", cam)
+    run_driver("transform_driver", tmp_path, env=NO_LEGACY_IPC)
+    rd = lambda name: read_f32(tmp_path, name)
 
     moved = pkg.transform_camera(cam, sim)
     got_view = rd("camera_moved").reshape(4, 4)
