@@ -36,5 +36,7 @@ from .lifting import (LiftedMaps, blend_lift, error_scores, lift_maps, lift_pixe
                       select_gaussians, vote_labels)
 from .transform import (Similarity, merge_gaussians, sh_rotation_matrices, similarity_from_cameras,  # noqa: F401
                         transform_camera, transform_cameras, transform_gaussians)
+from .compress import (CompressedGaussians, compress_gaussians, decompress_gaussians, nbytes,  # noqa: F401
+                       read_compressed, vq_assign, vq_fit, vq_frac_bits, vq_update, write_compressed)
 from .mesh import Mesh, TSDFView, TSDFVolume, extract_mesh, write_mesh_ply  # noqa: F401
 from . import parallel, scene  # noqa: F401

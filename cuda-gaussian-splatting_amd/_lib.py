@@ -228,6 +228,9 @@ SIGNATURES = {
     "cugs_similarity_init": (_I, [C.POINTER(Similarity), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double]),
     "cugs_transform_gaussians": (_I, [_L, _I, _P, _P, _P, _P, _P, C.POINTER(_P), C.POINTER(C.c_int), _I,
                                       C.POINTER(Similarity), _P]),
+    "cugs_vq_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "cugs_vq_assign": (_I, [_L, _I, _I, _P, _L, _P, _P, _P, _P, C.c_size_t, _P]),
+    "cugs_vq_update": (_I, [_L, _I, _I, _P, _L, _P, _P, _I, _P, _P, _P, C.c_size_t, _P]),
     "cugs_device_count": (_I, [C.POINTER(C.c_int)]),
 }
 

@@ -469,4 +469,21 @@ cugs_camera transform_camera(const cugs_camera& camera, const Similarity& sim);
 // cleared.  Returns the new N.
 int64_t merge_gaussians(ModelTensors& model, const ModelTensors& other, FusedAdam* optimizer = nullptr);
 
+// Vector quantisation of rows of up to 48 floats (not in the reference; the arithmetic is stated in
+// cugs_hip.h).  x [n, d] float32 on a CUDA device (a row stride >= d is passed through), codebook [k, d].
+// vq_assign: int32 [n], the nearest code of every row, the lowest index among equals, 0 for a row holding a NaN;
+// `dist` (optional) receives the squared distance to it, float32 [n].
+torch::Tensor vq_assign(const torch::Tensor& x, const torch::Tensor& codebook, torch::Tensor* dist = nullptr);
+// The fraction bits of the fixed-point sums for n rows with |x| <= x_max and weights <= w_max: 61 minus the binary
+// exponents (frexp) of n and of max(w_max x_max, w_max), at most 62; throws where that is negative or not finite.
+int vq_frac_bits(int64_t n, double x_max, double w_max = 1.0);
+// Lloyd's k-means: {codebook [k', d], indices int32 [n], counts int32 [k']}, k' = min(k, n).  The first codebook is
+// `init` or the rows (j n) // k' of x; `iters` times assign and the deterministic update (weights: float32 [n],
+// non-negative, optional), then a last assign; counts is the histogram of the indices.  An empty code keeps its value.
+// One host read per call, none per iteration; the same bytes from run to run.  The container and compress_gaussians of
+// the Python host have no C++ counterpart yet.
+struct VqFit { torch::Tensor codebook, indices, counts; };
+VqFit vq_fit(const torch::Tensor& x, int64_t k, int iters = 10, const torch::Tensor& weights = {},
+             const torch::Tensor& init = {});
+
 }  // namespace cugs_hip

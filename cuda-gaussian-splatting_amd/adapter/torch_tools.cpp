@@ -1,5 +1,5 @@
-// torch_tools.cpp — cugs_hip_torch.hpp: TSDF fusion and mesh extraction, contribution scores, lifted pixel maps and the
-// similarity transform.
+// torch_tools.cpp — cugs_hip_torch.hpp: TSDF fusion and mesh extraction, contribution scores, lifted pixel maps, the
+// similarity transform and vector quantisation.
 #include "torch_glue.hpp"
 
 namespace cugs_hip {
@@ -412,6 +412,101 @@ int64_t merge_gaussians(ModelTensors& model, const ModelTensors& other, FusedAda
         optimizer->zero_grad();
     }
     return model.positions.size(0);
+}
+
+// ---- vector quantisation ----
+namespace {
+torch::Tensor vq_rows(const torch::Tensor& x, const char* what) {
+    TORCH_CHECK(x.defined() && x.dim() == 2, what, " must be a 2-D tensor");
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kFloat32, what, " must be float32 on a CUDA device");
+    TORCH_CHECK(x.size(1) >= 1 && x.size(1) <= 48, what, ": 1 <= d <= 48, got ", x.size(1));
+    if (x.size(0) <= 1 || x.stride(1) != 1 || x.stride(0) < x.size(1)) return x.contiguous();
+    return x;
+}
+int64_t vq_ldx(const torch::Tensor& x) { return x.size(0) > 1 ? x.stride(0) : x.size(1); }
+torch::Tensor vq_workspace(int64_t k, int64_t d, const torch::Tensor& like) {
+    const size_t bytes = cugs_vq_workspace_bytes(static_cast<int>(k), static_cast<int>(d));
+    TORCH_CHECK(bytes > 0, "vq: no workspace for k = ", k, ", d = ", d);
+    return torch::empty({static_cast<int64_t>(bytes)}, torch::TensorOptions().dtype(torch::kUInt8).device(like.device()));
+}
+void vq_assign_into(const torch::Tensor& x, const torch::Tensor& codebook, torch::Tensor& assign, torch::Tensor* dist,
+                    torch::Tensor& ws) {
+    check(cugs_vq_assign(x.size(0), static_cast<int>(x.size(1)), static_cast<int>(codebook.size(0)), ptr<float>(x), vq_ldx(x),
+                         ptr<float>(codebook), ptr<int32_t>(assign), dist ? ptr<float>(*dist) : nullptr, ws.data_ptr(),
+                         static_cast<size_t>(ws.numel()), stream_of(x)), "cugs_vq_assign");
+}
+}  // namespace
+
+torch::Tensor vq_assign(const torch::Tensor& x_in, const torch::Tensor& codebook_in, torch::Tensor* dist) {
+    torch::NoGradGuard no_grad;
+    const auto x = vq_rows(x_in, "x");
+    TORCH_CHECK(codebook_in.defined() && codebook_in.dim() == 2 && codebook_in.size(1) == x.size(1), "vq_assign: codebook must be [k, d]");
+    TORCH_CHECK(codebook_in.device() == x.device() && codebook_in.scalar_type() == torch::kFloat32,
+                "vq_assign: codebook must be float32 on the device of x");
+    const int64_t k = codebook_in.size(0), n = x.size(0);
+    TORCH_CHECK(k >= 1 && k <= 65536, "vq_assign: 1 <= k <= 65536, got ", k);
+    const auto codebook = codebook_in.contiguous();
+    auto assign = torch::empty({n}, iopt(x));
+    if (dist) *dist = torch::empty({n}, fopt(x));
+    if (n > 0) {
+        auto ws = vq_workspace(k, x.size(1), x);
+        vq_assign_into(x, codebook, assign, dist, ws);
+    }
+    return assign;
+}
+
+int vq_frac_bits(int64_t n, double x_max, double w_max) {
+    TORCH_CHECK(std::isfinite(x_max) && std::isfinite(w_max) && w_max >= 0.0,
+                "vq_fit: the data and the weights must be finite and the weights non-negative");
+    const double big = std::max(w_max * x_max, w_max);
+    if (big <= 0.0) return 62;
+    int en = 0, eb = 0;
+    std::frexp(static_cast<double>(std::max<int64_t>(n, 1)), &en);
+    std::frexp(big, &eb);
+    const int bits = 61 - en - eb;
+    TORCH_CHECK(bits >= 0, "vq_fit: n * max|w x| is too large for 64-bit fixed-point sums");
+    return std::min(bits, 62);
+}
+
+VqFit vq_fit(const torch::Tensor& x_in, int64_t k, int iters, const torch::Tensor& weights_in, const torch::Tensor& init) {
+    torch::NoGradGuard no_grad;
+    const auto x = vq_rows(x_in, "x");
+    const int64_t n = x.size(0), d = x.size(1);
+    TORCH_CHECK(k >= 1 && k <= 65536, "vq_fit: 1 <= k <= 65536, got ", k);
+    TORCH_CHECK(iters >= 0, "vq_fit: iters must not be negative");
+    const int64_t kk = std::min(k, n);
+    torch::Tensor weights;
+    if (weights_in.defined()) {
+        TORCH_CHECK(weights_in.numel() == n && weights_in.device() == x.device(),
+                    "vq_fit: weights must hold one value per row, on the device of x");
+        weights = weights_in.reshape({n}).to(torch::kFloat32).contiguous();
+    }
+    if (n == 0) return {torch::empty({0, d}, fopt(x)), torch::empty({0}, iopt(x)), torch::empty({0}, iopt(x))};
+    torch::Tensor codebook;
+    if (init.defined()) {
+        TORCH_CHECK(init.dim() == 2 && init.size(0) == kk && init.size(1) == d, "vq_fit: init must be [", kk, ", ", d, "]");
+        codebook = init.to(x.device(), torch::kFloat32).contiguous().clone();
+    } else {
+        const auto first = (torch::arange(kk, torch::TensorOptions().dtype(torch::kInt64).device(x.device())) * n).floor_divide(kk);
+        codebook = x.index_select(0, first).contiguous();
+    }
+    std::vector<torch::Tensor> top = {x.abs().max()};
+    if (weights.defined()) { top.push_back(weights.max()); top.push_back(weights.min()); }
+    const auto host = torch::stack(top).to(torch::kCPU);            // the one host read of a fit
+    const float* hv = host.data_ptr<float>();
+    TORCH_CHECK(!weights.defined() || hv[2] >= 0.0f, "vq_fit: the weights must be non-negative");
+    const int frac_bits = vq_frac_bits(n, hv[0], weights.defined() ? hv[1] : 1.0);
+    auto ws = vq_workspace(kk, d, x);
+    auto assign = torch::empty({n}, iopt(x));
+    for (int it = 0; it < iters; ++it) {
+        vq_assign_into(x, codebook, assign, nullptr, ws);
+        check(cugs_vq_update(n, static_cast<int>(d), static_cast<int>(kk), ptr<float>(x), vq_ldx(x), ptr<float>(weights),
+                             ptr<int32_t>(assign), frac_bits, ptr<float>(codebook), nullptr, ws.data_ptr(),
+                             static_cast<size_t>(ws.numel()), stream_of(x)), "cugs_vq_update");
+    }
+    vq_assign_into(x, codebook, assign, nullptr, ws);
+    auto counts = torch::bincount(assign.to(torch::kInt64), {}, kk).to(torch::kInt32);
+    return {codebook, assign, counts};
 }
 
 }  // namespace cugs_hip

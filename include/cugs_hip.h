@@ -993,6 +993,46 @@ int cugs_transform_gaussians(int64_t n, int sh_coeffs, float* positions, float* 
                              const uint8_t* mask /* nullable */, float* const* zero_rows_host,
                              const int* zero_row_floats_host, int num_zero, const CugsSimilarity* xf_host, void* stream);
 
+/* ---- vector quantisation: nearest-code assignment and a deterministic Lloyd update (not in the reference; DESIGN.md
+ * 4.27) ----------------------------------------------------------------------------------------------------------------
+ * x [n, d] fp32 with a row stride of ldx >= d floats, codebook [k, d] fp32 contiguous, 1 <= d <= 48, 1 <= k <= 65536,
+ * 0 <= n <= 2^31 - 1.  cugs_vq_workspace_bytes(k, d): scratch for either call (the int64 sums, 0.5 |c|^2 and the
+ * codebook repacked for the matrix pipe; a multiple of 256, monotone in k and in d, 0 for a k or d outside the limits).
+ *
+ * cugs_vq_assign (two launches, a third with dist; no host sync):
+ *   dot(i,j)   acc = 0; for t = 0..d-1 ascending: acc = fmaf(x[i,t], c[j,t], acc)
+ *              (computed by v_mfma_f32_32x32x2_f32, which is that chain bit for bit; d is padded with zeros to an even
+ *              length, and fmaf(0, 0, acc) changes no comparison)
+ *   h[j]       0.5f * (acc = 0; acc = fmaf(c[j,t], c[j,t], acc), t ascending)
+ *   score(i,j) h[j] - dot(i,j), one fp32 subtraction
+ *   assign[i]  the j of the smallest score, the lowest j among equal scores: a strict < against a running best that
+ *              starts at (+inf, 0), pairs (score, index) merged lexicographically wherever partial results meet.  A row
+ *              whose scores are all NaN (a NaN in the row) therefore gets 0.
+ *   dist[i]    (nullable) acc = 0; for t ascending: df = x[i,t] - c[a,t]; acc = acc + df * df, for the winner a; the
+ *              subtraction, the product and the sum each rounded to fp32 on its own.
+ *
+ * cugs_vq_update (three launches, no host sync): with F = frac_bits (0..62) and w_i = 1 where weights is NULL,
+ *   num[j,t] = sum over i with assign[i] = j of (int64) rint((double) w_i * (double) x[i,t] * 2^F)
+ *   den[j]   = sum over the same i of (int64) rint((double) w_i * 2^F)
+ *   codebook[j,t] = (float) ((double) num[j,t] / (double) den[j]) where den[j] > 0; a code with den[j] <= 0 (no member,
+ *   or members of weight 0 only) keeps its bits: it is not re-seeded.  counts [k] int32 (nullable) receives the number of
+ *   rows assigned to each code, whatever their weight.  A row whose assign is outside [0, k) is skipped - neither it nor
+ *   anything through it is touched; -1 is the mark for "leave this row out".  The sums are two's complement integers
+ *   added by 64-bit integer atomics, so the result does not depend on the order of the additions: the same bytes from
+ *   run to run.  The call clears the sums it uses itself.  The caller guarantees n max|w x| 2^F < 2^62 and
+ *   n max w 2^F < 2^62 (no overflow of a sum), and finite non-negative weights.
+ *
+ * Checks, before anything is queued, in this order: CUGS_EINVAL for n, d, k, ldx or frac_bits outside the limits above,
+ * or with n > 0 a NULL x, codebook, assign or workspace; CUGS_EWORKSPACE for workspace_bytes below
+ * cugs_vq_workspace_bytes(k, d); CUGS_EALIGN for a pointer that is not dword aligned or a workspace that is not 8-byte
+ * aligned; n = 0 then returns 0 with nothing queued. */
+size_t cugs_vq_workspace_bytes(int k, int d);
+int cugs_vq_assign(int64_t n, int d, int k, const float* x, int64_t ldx, const float* codebook, int32_t* assign,
+                   float* dist /* nullable */, void* workspace, size_t workspace_bytes, void* stream);
+int cugs_vq_update(int64_t n, int d, int k, const float* x, int64_t ldx, const float* weights /* nullable */,
+                   const int32_t* assign, int frac_bits, float* codebook /* in, out */, int32_t* counts /* nullable */,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* Device properties the host side needs without linking the HIP runtime itself. */
 int cugs_device_count(int* count_host);
 
