@@ -22,6 +22,9 @@ from .loss import (DepthLoss, ExposureLoss, NormalLoss, combined_loss, combined_
 from .exposure import ExposureModel  # noqa: F401
 from .bilagrid import (BilagridGrad, BilateralGridModel, bilagrid_slice, bilagrid_slice_backward,  # noqa: F401
                        bilagrid_tv)
+from .envmap import (EnvGrad, EnvironmentMap, composite_background, composite_background_backward,  # noqa: F401
+                     composite_environment, composite_environment_backward, envmap_frac_bits,
+                     render_with_environment)
 from .densification import DensificationConfig, DensificationController, DensificationStats  # noqa: F401
 from .mcmc import MCMCConfig, MCMCController, MCMCStats  # noqa: F401
 from .gaussian_init import init_gaussians_from_sparse, knn_mean_distances  # noqa: F401

@@ -128,6 +128,13 @@ class BilagridDims(C.Structure):
     """struct cugs_bilagrid_dims."""
     _fields_ = [("l", C.c_int32), ("gy", C.c_int32), ("gx", C.c_int32)]
 
+
+class EnvmapView(C.Structure):
+    """struct cugs_envmap_view."""
+    _fields_ = [("m", C.c_float * 9), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32), ("resolution", C.c_int32)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _L = C.c_int64
@@ -231,6 +238,11 @@ SIGNATURES = {
     "cugs_vq_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cugs_vq_assign": (_I, [_L, _I, _I, _P, _L, _P, _P, _P, _P, C.c_size_t, _P]),
     "cugs_vq_update": (_I, [_L, _I, _I, _P, _L, _P, _P, _I, _P, _P, _P, C.c_size_t, _P]),
+    "cugs_envmap_view_init": (_I, [C.POINTER(EnvmapView), C.POINTER(Camera), C.POINTER(C.c_double), _I]),
+    "cugs_envmap_workspace_bytes": (C.c_size_t, [_I]),
+    "cugs_envmap_frac_bits": (_I, [_I, _I, _F]),
+    "cugs_envmap_composite": (_I, [C.POINTER(EnvmapView), _P, _P, _P, _P, _P, _P, _P]),
+    "cugs_envmap_composite_backward": (_I, [C.POINTER(EnvmapView), _P, _P, _P, _P, _F, _P, C.c_size_t, _P, _P, _P, _P, _P]),
     "cugs_device_count": (_I, [C.POINTER(C.c_int)]),
 }
 

@@ -233,6 +233,48 @@ BilagridGrad bilagrid_slice_backward(const torch::Tensor& grid, const torch::Ten
                                      bool want_image_grad = true);
 BilagridTV bilagrid_tv(const torch::Tensor& grid, float weight = 1.0f, const torch::Tensor& dL_dgrid = {});
 
+// Not in the reference: an environment-map background.  The model is rendered on background 0 (the
+// blend leaves color = C); composite_environment adds the sky behind it, image = fmaf(final_T, B, color) with B the
+// bilinear sample of one octahedral map [3, R, R] (R a power of two in [4, 2048]; the centre is the map frame's +z, the
+// corners its -z) in the direction of each pixel's ray - one launch, a uniform map of colour c giving render(background
+// = c) bit for bit.  composite_environment_backward: dL_dalpha = -sum_c g_c B_c for render_backward (with dL_dimage as
+// its dL_dcolor), dL_denv summed in 64-bit fixed point through integer atomics (the same bytes from run to run, no host
+// sync) and `clamped`, a 0-dim int32 device word set when a share T g_c w_k exceeded grad_bound (rounded up to a power
+// of two; it fixes the scale, cugs_envmap_frac_bits).  composite_background / _backward do the same for a caller's
+// background image [H,W,3]: dL_dbackground = T g.  The composites refuse a RenderSettings whose background is not 0.
+// The step: render_with_environment -> loss and g -> composite_environment_backward -> render_backward(g, ...,
+// dL_dalpha) and env.step(dL_denv, lr).
+class EnvironmentMap {
+public:
+    // `orientation`: row-major 3x3, world axes to map axes (nullptr: identity); init_color fills the map
+    EnvironmentMap(int resolution, const torch::Device& device, const float init_color[3] = nullptr,
+                   const double* orientation = nullptr);
+    torch::Tensor& texture() { return texture_; }
+    const torch::Tensor& texture() const { return texture_; }
+    int resolution() const { return static_cast<int>(texture_.size(1)); }
+    const std::array<double, 9>& orientation() const { return orientation_; }
+    cugs_envmap_view view(const cugs_camera& camera) const;             // M = orientation R^T rounded once, intrinsics, sizes
+    torch::Tensor sample(const cugs_camera& camera) const;              // B [H,W,3]
+    void step(const torch::Tensor& dL_denv, float lr);                  // one fused Adam update (AdamHyper's defaults), moments inside
+private:
+    torch::Tensor texture_, m_, v_;
+    std::array<double, 9> orientation_;
+    int step_count_ = 0;
+};
+struct EnvGrad { torch::Tensor dL_dalpha, dL_denv, clamped; };
+struct BackgroundGrad { torch::Tensor dL_dalpha, dL_dbackground; };
+struct EnvRender { torch::Tensor image; RenderOutput render_out; };
+torch::Tensor composite_environment(const RenderOutput& render_out, const cugs_camera& camera, const EnvironmentMap& env,
+                                    const RenderSettings* settings = nullptr);
+EnvGrad composite_environment_backward(const torch::Tensor& dL_dimage, const RenderOutput& render_out,
+                                       const cugs_camera& camera, const EnvironmentMap& env, float grad_bound = 1.0f,
+                                       bool want_env_grad = true, const RenderSettings* settings = nullptr);
+torch::Tensor composite_background(const torch::Tensor& color, const torch::Tensor& final_T, const torch::Tensor& background);
+BackgroundGrad composite_background_backward(const torch::Tensor& dL_dimage, const torch::Tensor& final_T,
+                                             const torch::Tensor& background, bool want_background_grad = true);
+EnvRender render_with_environment(const ModelTensors& model, const cugs_camera& camera, const RenderSettings& settings,
+                                  const EnvironmentMap& env, bool for_backward = true, bool want_depth_map = false);
+
 // optimizer/fused_adam.hpp:29-106 on raw tensors (group order: positions, sh, opacities, scales, rotations)
 struct AdamHyper { float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-15f; };
 class FusedAdam {

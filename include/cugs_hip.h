@@ -1033,6 +1033,60 @@ int cugs_vq_update(int64_t n, int d, int k, const float* x, int64_t ldx, const f
                    const int32_t* assign, int frac_bits, float* codebook /* in, out */, int32_t* counts /* nullable */,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- environment-map background: octahedral sky, fused composite and gradients (not in the reference) --
+ * The Gaussians are rendered on background 0, so the blend leaves color = C; the final image is I = C + T B(p), B the
+ * bilinear sample of one octahedral map E [3, R, R] fp32 (R a power of two, 4..2048) in the direction of pixel p's ray,
+ * or a caller's background image [H, W, 3].  color, image, sample, dL_dimage, background: [H, W, 3]; final_T, dL_dalpha:
+ * [H, W].  Every step is one correctly rounded fp32 operation (fmaf where written); tests/envmap_ref.py mirrors it bit for
+ * bit.  For pixel (u, v):
+ *   1. ax = (((float) u + 0.5f) - cx) / fx,  ay = (((float) v + 0.5f) - cy) / fy        (the blend's pixel centre)
+ *   2. d_k = fmaf(m[3k], ax, fmaf(m[3k+1], ay, m[3k+2])), k = 0..2: m = O R^T, rows of the map's axes in camera
+ *      coordinates.  cugs_envmap_view_init forms it in fp64 from the camera's world-to-camera rotation R and the
+ *      orientation O (world to map axes, row-major, NULL = identity): m[3i+j] = (float) ((O[i][0] R[j][0] + O[i][1] R[j][1])
+ *      + O[i][2] R[j][2]), one rounding to fp32.
+ *   3. s = (|d0| + |d1|) + |d2|;  n = d / s (three divisions).  If n2 < 0: x = (1 - |n1|) sgn(n0), y = (1 - |n0|) sgn(n1),
+ *      sgn(t) = t >= 0 ? 1 : -1; otherwise x = n0, y = n1.  (s not in (0, inf): x = y = 0.)
+ *   4. h = 0.5f R;  sx = fmaf(x, h, h - 0.5f), i0 = floorf(sx) held to [-1, R - 1], a = sx - (float) i0;  sy, j0, b
+ *      likewise from y.  Taps (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1): E00, E01, E10, E11.
+ *   5. a tap outside [0, R) is folded by the octahedral rule:  i < 0: (i, j) = (-1 - i, R - 1 - j);  i >= R: (2R - 1 - i,
+ *      R - 1 - j);  then j < 0: (i, j) = (R - 1 - i, -1 - j);  j >= R: (R - 1 - i, 2R - 1 - j).  Texel (i, j) of channel c
+ *      is E[(c R + j) R + i].
+ *   6. top = fmaf(a, E01 - E00, E00), bot = fmaf(a, E11 - E10, E10), B_c = fmaf(b, bot - top, top)
+ *   7. I_c = fmaf(T, B_c, C_c)
+ * Backward, g = dL_dimage:
+ *   dL_dalpha = -fmaf(g2, B2, fmaf(g1, B1, g0 * B0))
+ *   dL_dbackground_c = T * g_c                                                             (the image route)
+ *   dL_denv: tap k of channel c receives the share  w_k * (T * g_c),  w00 = (1 - a) * (1 - b), w01 = a * (1 - b),
+ *   w10 = (1 - a) * b, w11 = a * b, as the integer rint((double) share * 2^F) added by 64-bit integer atomics, and
+ *   dL_denv = (float) ((double) sum * 2^-F): the same bytes from run to run.  With 2^e the smallest power of two >=
+ *   grad_bound and 2^q the smallest power of two > 4 H W, F = 61 - q - e (cugs_envmap_frac_bits).  A share beyond
+ *   +-2^e is clamped to it (a NaN share counts 0) and sets *clamped (device int32, written every call) to 1.
+ *
+ * cugs_envmap_workspace_bytes(R): the int64 table of the map gradient; 0 for a bad R.
+ * cugs_envmap_composite: exactly one of env and background.  image needs color and final_T; sample (env route only,
+ * nullable) receives B itself; at least one of image and sample.
+ * cugs_envmap_composite_backward: exactly one of env and background; dL_dalpha, dL_denv (env route; needs workspace and
+ * clamped) and dL_dbackground (image route) are each nullable.  Three launches with dL_denv, one without; no host sync.
+ * Checks, before anything is queued, in this order: CUGS_EINVAL (NULL view or required pointer, width or height <= 0,
+ * on the env route R not a power of two in [4, 2048] or fx, fy not positive and finite or cx, cy, m not finite,
+ * grad_bound not in [2^-60, 2^24]); CUGS_EOVERFLOW for H W > 2^31 - 1; CUGS_EWORKSPACE; CUGS_EALIGN for a pointer that
+ * is not dword aligned or a workspace that is not 8-byte aligned. */
+typedef struct cugs_envmap_view {
+    float m[9];
+    float fx, fy, cx, cy;
+    int32_t width, height, resolution;     /* resolution is not read on the image route */
+} cugs_envmap_view;
+int cugs_envmap_view_init(cugs_envmap_view* out, const cugs_camera* camera, const double* orientation /* [9], nullable */,
+                          int resolution);
+size_t cugs_envmap_workspace_bytes(int resolution);
+int cugs_envmap_frac_bits(int width, int height, float grad_bound);      /* F, or a negative error code */
+int cugs_envmap_composite(const cugs_envmap_view* view, const float* env, const float* background, const float* color,
+                          const float* final_T, float* image /* nullable */, float* sample /* nullable */, void* stream);
+int cugs_envmap_composite_backward(const cugs_envmap_view* view, const float* env, const float* background,
+                                   const float* dL_dimage, const float* final_T, float grad_bound, void* workspace,
+                                   size_t workspace_bytes, float* dL_dalpha, float* dL_denv, float* dL_dbackground,
+                                   int32_t* clamped, void* stream);
+
 /* Device properties the host side needs without linking the HIP runtime itself. */
 int cugs_device_count(int* count_host);
 
